@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — Mray/s of the wavefront path tracer on BASELINE.json's configs[1].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds everything else the
+benchmark measures, each from runs of its own after the timed region: the roofline object (stats build of the same
+batch, the batch as one lane, the other pipeline), the CPU baselines and the other BASELINE configurations.
+--dump-outputs DIR writes what the timed steps computed (the frame and the job's ray counters, below) as .npy files.
 
 Workload (config.workload): samples/cornellbox.usda at 1920x1080, scene-default depth 32, triangle filter r=1,
 adaptive stopping off (variance 0), frame 0. A "step" is ONE wavefront batch: `--spp-per-step` samples (default
@@ -31,6 +36,12 @@ HIP-event duration of its launches in the timed region; `bound` / `peak` / `frac
 bytes according to the committed PMC passes of this build (HBM when the measured fabric traffic reaches 30 % of its
 8 TB/s, else the L2 aggregate with bound "latency/issue"); the other stages' figures are under roofline.kernels. cpu_baseline: the
 oracle (CPU restatement, "port") rendering a bounded sample of the same workload on this box's host cores.
+
+--dump-outputs DIR (rank 0): frame.npy, the resolved film after the last timed step ([height, width, 3] float32, bottom
+row first) — or, where that exceeds 64 MB, frame_sample.npy with a fixed seeded sample of its pixels ([k, 3] float32)
+and frame_sample_pixels.npy with their indices (float64); ray_stats.npy, the job's eight RayStats counters over the
+timed steps (float64, in stats.rs order). The scene, the sampler seeds and the frame are fixed, so the same arguments
+give the same inputs on every run.
 """
 import argparse
 import json
@@ -55,18 +66,24 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--scene", default="cornellbox")
     ap.add_argument("--depth", type=int, default=None, help="override max depth (default: the scene's, 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, the CPU baselines and the other configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed steps computed (frame, ray counters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-spp", type=int, default=24, help="spp of the bounded CPU-baseline sample (per run; 3 runs of 24 spp are ~10 s on 16 cores)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = this box's share: min(affinity, 16 per GPU))")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1; gloo (CPU tensors, ranks may share a GPU) rehearses the N > 1 path on a 1-GPU box")
     ap.add_argument("--cpu-reps", type=int, default=3, help="the CPU baseline is the best of this many runs (BASELINE.md §3: min of 3)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the other BASELINE configurations that follow the headline at N=1 (other_configs)")
+                    help="--full without the other BASELINE configurations that follow the headline at N=1 (other_configs)")
     ap.add_argument("--other-configs-scale", type=int, default=1,
                     help="divide the other configurations' width and height by this and their spp by its square (tests)")
     ap.add_argument("--dump-frame", default=None, help="rank 0 writes the gathered frame ([height*width, 3] float32, .npy) here")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU) and relay rank 0's
@@ -128,7 +145,8 @@ def main():
         sample += spp_step
     barrier()
     r.clear(stream)  # film sums and ray counters restart; buffers stay resident
-    r.profile(True)
+    if args.full:  # HIP events around every launch: the roofline's per-kernel times
+        r.profile(True)
     n_pix_total = args.width * args.height
     d_rgb = torch.empty(r.n_pix * 3, dtype=torch.float32, device="cuda")
     plan = crt.shard.GatherPlan(args.width, args.height, world, coll) if dist is not None else None
@@ -145,12 +163,16 @@ def main():
         frame = plan.gather(d_rgb.reshape(-1, 3).to(coll), dist, dst=0)
     barrier()
     elapsed = time.perf_counter() - t0
-    if args.dump_frame and rank == 0:
+    if (args.dump_frame or args.dump_outputs) and rank == 0:
         full = frame if frame is not None else crt.shard.GatherPlan(args.width, args.height, 1, "cuda").gather(d_rgb.reshape(-1, 3))
-        np.save(args.dump_frame, full.cpu().numpy())
+        frame = full.cpu().numpy()
+        if args.dump_frame:
+            np.save(args.dump_frame, frame)
     st = r.stats()
-    prof = r.profile_read()
-    r.profile(False)
+    prof = None
+    if args.full:
+        prof = r.profile_read()
+        r.profile(False)
     # what the job cost to set up and to hold, per rank (max over ranks): the import (rank 0 parses, the others wait for the
     # broadcast), every rank's own commit, and the HBM this rank's scene image + path state + film occupy
     setup["hbm_used_gb"] = (hbm_free0 - torch.cuda.mem_get_info()[0]) / 1e9
@@ -171,6 +193,17 @@ def main():
     value = total_rays / elapsed / 1e6
 
     if rank != 0:
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame.reshape(args.height, args.width, 3), all_stats)
+
+    settings_depth = r.settings.max_depth
+    n_pix = r.n_pix
+    if not args.full:
+        print(json.dumps(headline(args, path, world, value, elapsed, spp_step, requested, settings_depth, n_pix, rays,
+                                  total_rays, stat_names, all_stats, setup)))
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -204,8 +237,6 @@ def main():
     dominant = max(kernels, key=lambda k: kernels[k]["total_ms"]) if kernels else None
     # the other pipeline on the same workload, 2 untimed steps: per-stage split of a fused step / the fused kernel's time.
     # The timed renderer's buffers (174 GB at the default shape) are released first.
-    settings_depth = r.settings.max_depth
-    n_pix = r.n_pix
     del r
     stage = other = None
     # With lanes the launches of the timed region overlap: a launch's own duration then includes the time it shares the
@@ -316,7 +347,18 @@ def main():
             except Exception as e:  # noqa: BLE001  (informational: the headline still prints)
                 others.append({"workload": "%s %dx%d %dspp" % (scene, w, h, spp), "error": "%s: %s" % (type(e).__name__, e)})
 
-    out = {
+    out = headline(args, path, world, value, elapsed, spp_step, requested, settings_depth, n_pix, rays, total_rays, stat_names,
+                   all_stats, setup)
+    out.update(roofline=roofline, cpu_baseline=cpu, cpu_baseline_all_cores=cpu_all, other_configs=others)
+    print(json.dumps(out))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def headline(args, path, world, value, elapsed, spp_step, requested, settings_depth, n_pix, rays, total_rays, stat_names,
+             all_stats, setup):
+    """The result line of a plain run: the headline rate, its timing and the workload it was measured on."""
+    return {
         "metric": "Mray/s (closest-hit + shadow queries) of the path-tracing integrator",
         "value": round(value, 2),
         "unit": "Mray/s",
@@ -352,14 +394,28 @@ def main():
             "setup": setup,
             "sharding": ("16x16 pixel tiles round-robin over ranks; one %s gather of tile buffers to rank 0" % ("RCCL" if args.backend == "nccl" else "gloo (rehearsal)")) if world > 1 else "none",
         },
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-        "cpu_baseline_all_cores": cpu_all,
-        "other_configs": others,
     }
-    print(json.dumps(out))
-    if dist is not None:
-        dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, frame, ray_stats):
+    """--dump-outputs: the resolved frame ([height, width, 3] float32) and the eight RayStats totals (float64) as .npy
+    files in out_dir. A frame larger than the limit is written as a fixed seeded sample of its pixels plus their
+    indices, so two builds can still be compared pixel for pixel."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES - (1 << 20):
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+    else:
+        pixels = frame.reshape(-1, 3)
+        k = (DUMP_LIMIT_BYTES - (1 << 20)) // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(pixels), size=k, replace=False))
+        np.save(os.path.join(out_dir, "frame_sample.npy"), pixels[idx])
+        np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "ray_stats.npy"), np.asarray(ray_stats, dtype=np.float64))
 
 
 # (scene, width, height, spp per step): BASELINE.json configs[2..4] at their own resolutions + the reference's stress

@@ -1,4 +1,5 @@
-"""The driver's bench.py contract: one JSON line with the required keys, roofline and cpu_baseline objects."""
+"""The driver's bench.py contract: one JSON line with the required keys; with --full also the roofline and cpu_baseline
+objects."""
 import json
 import os
 import subprocess
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "192",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--width", "192",
                           "--height", "108", "--spp-per-step", "4", "--cpu-spp", "1", "--other-configs-scale", "16"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -64,6 +65,52 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert set(d["config"]["setup"]) == {"import_s", "commit_s", "hbm_used_gb_per_rank"} and d["config"]["setup"]["hbm_used_gb_per_rank"] > 0
     # rays are counted as the reference counts them (stats.rs:150-152)
     assert d["config"]["rays_total"] == d["config"]["closest_hit"] + d["config"]["shadow_rays"]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """Without --full the line holds the headline and its workload, nothing that takes runs of its own; --dump-outputs
+    writes the frame the timed steps resolved (the same pixels --dump-frame writes) and the job's ray counters."""
+    import numpy as np
+    out, f = tmp_path / "out", str(tmp_path / "frame.npy")
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "192",
+                          "--height", "108", "--spp-per-step", "4", "--dump-outputs", str(out), "--dump-frame", f],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "cpu_baseline_all_cores", "other_configs"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Mray/s" and d["dtype"] == "f32" and d["value"] > 0
+    assert abs(d["ms_per_step"] - d["config"]["seconds"] / 3 * 1e3) < 0.05  # seconds is rounded to 0.1 ms
+    assert d["config"]["camera_rays"] == 192 * 108 * 4 * 3  # the three timed steps, nothing else
+    assert sorted(os.listdir(out)) == ["frame.npy", "ray_stats.npy"]
+    img, rs = np.load(out / "frame.npy"), np.load(out / "ray_stats.npy")
+    assert img.dtype == np.float32 and img.shape == (108, 192, 3)
+    assert np.array_equal(img.reshape(-1, 3).view(np.uint32), np.load(f).view(np.uint32))
+    assert rs.dtype == np.float64 and list(rs) == list(d["config"]["ray_stats"].values())
+
+
+def test_dump_outputs_samples_a_frame_above_the_limit(tmp_path, monkeypatch):
+    """A frame larger than the dump limit is written as the same seeded sample of its pixels on every run (CPU-only)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (1 << 20) + 20 * 100)
+    frame = np.arange(60 * 40 * 3, dtype=np.float32).reshape(60, 40, 3)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), frame, [1, 2, 3, 4, 5, 6, 7, 8])
+    assert sorted(os.listdir(tmp_path / "a")) == ["frame_sample.npy", "frame_sample_pixels.npy", "ray_stats.npy"]
+    px, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_pixels.npy")
+    assert px.dtype == np.float32 and px.shape == (100, 3) and idx.dtype == np.float64 and len(np.unique(idx)) == 100
+    assert np.array_equal(px, frame.reshape(-1, 3)[idx.astype(np.int64)])
+    for n in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    bench.dump_outputs(str(tmp_path / "c"), frame[:4], range(8))  # small enough: the whole frame
+    assert np.array_equal(np.load(tmp_path / "c" / "frame.npy"), frame[:4])
 
 
 @pytest.mark.gpu
