@@ -20,8 +20,10 @@
 //
 // Float contract: this header must be compiled with -ffp-contract=off. Every expression below is
 // written in the reference's operation order; the watertightness argument (triangle.rs:88-96) and the
-// bit-for-bit parity with the CPU oracle both depend on it. Slab min/max use v_min/v_max: they differ
-// from SSE minps/maxps only in the sign of a zero result, which no comparison downstream can see.
+// bit-for-bit parity with the CPU oracle both depend on it. Slab min/max use v_min/v_max: for finite operands they
+// differ from SSE minps/maxps only in the sign of a zero result, which no comparison downstream can see; a NaN operand
+// (a ray with a NaN or an infinity in it) is dropped by v_min/v_max where SSE may return it, so such a ray can visit
+// other nodes than the reference's (tests/test_gpu_edge_rays.py).
 #pragma once
 
 #include <hip/hip_runtime.h>

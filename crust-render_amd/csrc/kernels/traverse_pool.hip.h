@@ -64,7 +64,11 @@ constexpr int kPoolStack = CRT_POOL_STACK;       // flat scenes (the three CRT_P
 constexpr int kPoolStackDeep = CRT_POOL_STACK_DEEP;  // instance-heavy scenes
 // Private part of the stack. sp lives in 8 bits of the ctl word, so LDS part + private part must not exceed 255 with
 // EITHER split: a push at the limit then takes the err path (CRT_ERR_STACK) instead of wrapping into `base`.
-constexpr int kPoolSpill = 255 - (kPoolStack > kPoolStackDeep ? kPoolStack : kPoolStackDeep);
+// -DCRT_POOL_SPILL=<n>: a smaller private part (tests of the overflow path, tests/test_gpu_stack_overflow.py).
+#ifndef CRT_POOL_SPILL
+#define CRT_POOL_SPILL (255 - (kPoolStack > kPoolStackDeep ? kPoolStack : kPoolStackDeep))
+#endif
+constexpr int kPoolSpill = CRT_POOL_SPILL;
 static_assert(kPoolStack + kPoolSpill <= 255 && kPoolStackDeep + kPoolSpill <= 255, "sp must fit the ctl word's 8 bits");
 constexpr int kFetchMin = CRT_FETCH_MIN;     // fetch new rays once this many lanes have a free slot
 #ifndef CRT_EMIT_BIAS
@@ -103,7 +107,7 @@ __device__ __forceinline__ uint32_t ctl_pack(uint32_t sp, uint32_t base, uint32_
   return sp | (base << 8) | (level << 16) | (hp << 19) | (kz << 20) | (swap << 22) | (lo << 24);
 }
 // the control word with a new stack position
-__device__ __forceinline__ uint32_t ctl_sp(uint32_t c, uint32_t sp, uint32_t lo) { return (c & 0x00ffff00u) | sp | (lo << 24); }
+__device__ __forceinline__ uint32_t ctl_sp(uint32_t c, uint32_t sp, uint32_t lo) { return (c & 0x00ffff00u) | (sp & 0xffu) | (lo << 24); }
 
 //   fetch(want, ray) -> bool : called by the whole wave; lanes with want==true may receive a ray
 //   emit(slot, hit?, Hit)    : called by a lane whose ray is finished (ANY: hit? means occluded)
@@ -478,20 +482,23 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
             } else if (!CRT_STACK_RING && CRT_SPILL_UNROLLED) {
               // deep stack: the same independent predicated writes, each to LDS or to the private part by its position
               // (rounds 1-3 ran a loop over the entries here — a select chain and a branchy push per entry, for every node
-              // step of a ray working below the LDS part of its stack)
+              // step of a ray working below the LDS part of its stack). All or nothing: when the entries below the top
+              // one do not all fit, none is stored and sp stays (CRT_ERR_STACK), the ray goes on with the top entry —
+              // so sp never passes pstack + kPoolSpill and every later pop reads an entry that was stored.
+              const bool fits = sp + n_tot - 1 <= pstack + (uint32_t)kPoolSpill;
+              if (!fits) err |= 1u;
 #pragma unroll
               for (int i = 0; i < 4; i++) {
                 if (on[i]) {
                   if (pos[i] == n_tot - 1) top_e = ent[i];
-                  else {
+                  else if (fits) {
                     const uint32_t at = sp + pos[i];
                     if (at < pstack) STK((int)at, row) = ent[i];
-                    else if (at - pstack < (uint32_t)kPoolSpill) spill[row][at - pstack] = ent[i];
-                    else err |= 1u;
+                    else spill[row][at - pstack] = ent[i];
                   }
                 }
               }
-              sp += n_tot - 1;
+              if (fits) sp += n_tot - 1;
             } else {  // one entry at a time through push()
               for (uint32_t k = 0; k < n_tot; k++) {
                 uint32_t e = 0;

@@ -39,7 +39,10 @@ typedef enum {
   CRT_ERR_BAD_ARG = -1,
   CRT_ERR_BAD_ID = -2,     /* scene.rs:197-201 (panic in the reference) */
   CRT_ERR_NO_DEVICE = -3,  /* no gfx950 HIP device / HIP call failed */
-  CRT_ERR_STACK = -4,      /* traversal stack capacity exceeded (never on trees the builder emits) */
+  CRT_ERR_STACK = -4,      /* traversal stack capacity exceeded: a ray had more pending entries (inner nodes and leaf
+                            * words of every instance level together) than its one device stack holds, 255 in the
+                            * shipped build. The reference's stack has no limit; deep trees of overlapping boxes and
+                            * nested instances can reach it */
   CRT_ERR_UNSUPPORTED = -5, /* RoundCurves / CubicCurves (scene.rs:99-106): out of scope */
   CRT_ERR_NO_MEMORY = -6    /* a host allocation failed (the reference aborts); reason in crt_last_error. Nothing unwinds
                              * through this ABI: a C or Rust host could not catch it */
@@ -170,8 +173,10 @@ int crt_intersect_n(CrtScene *s, const CrtRay *d_rays, size_t n, float t_min, fl
                     void *stream);
 int crt_occluded_n(CrtScene *s, const CrtRay *d_rays, size_t n, float t_min, float t_max, uint32_t *d_out,
                    void *stream);
-/* The batched forms do not synchronise, so they cannot report a traversal that overflowed its stack (more than 255
- * pending entries): the kernels OR that into the SCENE's error word. This call drains `stream`, reads and clears
+/* The batched forms do not synchronise, so they cannot report a traversal that overflowed its stack (more pending
+ * entries than the device stack holds, 255 in the shipped build, all instance levels and leaf words together; the
+ * builder does not bound the depth of its trees, so a deep or heavily nested scene can reach it): the kernels OR that
+ * into the SCENE's error word. This call drains `stream`, reads and clears
  * the word: CRT_OK, or CRT_ERR_STACK if any launch on this scene since the last call met the condition (the
  * affected rays' results are then undefined). The single-ray and *_stats forms check their own launches. */
 int crt_scene_traversal_error(CrtScene *s, void *stream);

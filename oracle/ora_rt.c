@@ -946,9 +946,10 @@ static int intersect_leaf(const Bvh *b, uint32_t leaf_idx, const OraRay *ray, co
     for (int lane = 0; lane < 4; lane++) {
       if (!(h.fallback & (1u << lane))) continue;
       OraPrimHit ph;
+      if (g_stats) g_stats->fallback_lanes++;
       if (prim_hit(&b->prims[pk->prim[lane]], ray, t_min, closest, &ph)) {
         closest = ph.t; *out = ph; found = 1;
-        if (g_stats) g_stats->accepted_hits++;
+        if (g_stats) { g_stats->accepted_hits++; g_stats->fallback_accepts++; }
       }
     }
   }
@@ -972,8 +973,14 @@ static int occlude_leaf(const Bvh *b, uint32_t leaf_idx, const OraRay *ray, cons
     const OraTri4 *pk = &b->packets[leaf->pkt_first + k];
     Hit4 h = tri4_intersect(pk, sh, ray->origin, ray->mask, t_min, t_max);
     if (h.hits) return 1;
-    for (int lane = 0; lane < 4; lane++)
-      if ((h.fallback & (1u << lane)) && prim_hit_any(&b->prims[pk->prim[lane]], ray, t_min, t_max)) return 1;
+    for (int lane = 0; lane < 4; lane++) {
+      if (!(h.fallback & (1u << lane))) continue;
+      if (g_stats) g_stats->fallback_lanes++;
+      if (prim_hit_any(&b->prims[pk->prim[lane]], ray, t_min, t_max)) {
+        if (g_stats) g_stats->fallback_accepts++;
+        return 1;
+      }
+    }
   }
   for (uint32_t k = 0; k < leaf->idx_count; k++)
     if (prim_hit_any(&b->prims[b->indices[leaf->idx_first + k]], ray, t_min, t_max)) return 1;

@@ -27,10 +27,14 @@ typedef struct { float t; v3 outward; float u, v; uint32_t geom_id, prim_id; } O
 /* scene.rs:134-142 */
 typedef struct { float t; v3 normal; int front_face; float u, v; uint32_t geom_id, prim_id; } OraRayHit;
 
-/* bvh.rs:53-57 traversal-stats mirror: index 0 = top level, 1 = inside an instance. */
+/* bvh.rs:53-57 traversal-stats mirror: index 0 = top level, 1 = inside an instance. The last two are coverage counters
+ * of the tests (not in the reference): packet lanes whose f32 edge function was exactly 0 and that were re-tested by
+ * the scalar watertight test with its f64 re-evaluation (triangle.rs:110-172, bvh.rs:551-561 / :636-643), and how many
+ * of those re-tests the traversal accepted (closest hit: the hit replaced the closest one; any hit: occluded). */
 typedef struct {
   uint64_t queries[2], nodes[2], leaves[2], packets[2], prims[2];
   uint64_t accepted_hits, instance_descents, stack_high_water;
+  uint64_t fallback_lanes, fallback_accepts;
 } OraTravStats;
 
 typedef struct OraScene OraScene;

@@ -55,7 +55,8 @@ class RayHit(C.Structure):
 class TravStats(C.Structure):
     _fields_ = [("queries", C.c_uint64 * 2), ("nodes", C.c_uint64 * 2), ("leaves", C.c_uint64 * 2),
                 ("packets", C.c_uint64 * 2), ("prims", C.c_uint64 * 2), ("accepted_hits", C.c_uint64),
-                ("instance_descents", C.c_uint64), ("stack_high_water", C.c_uint64)]
+                ("instance_descents", C.c_uint64), ("stack_high_water", C.c_uint64),
+                ("fallback_lanes", C.c_uint64), ("fallback_accepts", C.c_uint64)]  # coverage counters (ora_rt.h)
 
 
 class WideNode(C.Structure):
