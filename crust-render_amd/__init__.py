@@ -725,10 +725,11 @@ class Renderer:
         return {n: (int(w[k]), (l[k] / (64.0 * w[k])) if w[k] else 0.0) for k, n in enumerate(self.SHADE_CLASSES)}
 
     def pipeline(self):
-        """{'fused', 'wide', 'grid'}: the launch pipeline chosen for this scene (crt.h, crt_renderer_pipeline)."""
+        """{'fused', 'wide', 'shade_pipe', 'grid'}: the launch pipeline chosen for this scene (crt.h, crt_renderer_pipeline);
+        shade_pipe: the last batch's shade launches were the pipelined four-wave instance."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
-        return dict(fused=bool(out[0]), wide=bool(out[1]), grid=int(out[2]))
+        return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""

@@ -306,7 +306,7 @@ struct Knobs {
   // engine choice
   int wide = -1;              // CRT_WIDE
   // renderer
-  int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, shade_wide = -1, fused = -1;
+  int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, shade_wide = -1, shade_pipe = 1, fused = -1;
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
 };

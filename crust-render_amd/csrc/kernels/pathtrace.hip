@@ -327,6 +327,7 @@ constexpr int kClasses = 4;
 constexpr uint32_t kRing = 2 * kBlock;                 // entries per class ring: < kBlock pending + one classify batch
 constexpr int kRingDwords = kClasses * (int)kRing;
 constexpr int kClassLdsMax = 1024;                     // geom ids whose class byte is staged in LDS (1 KB)
+// (The pipelined four-wave instance has a budget of its own — staging blocks instead of class rings: kPipeMatMax below.)
 constexpr int mat_lds_max(int arena) { return (arena - kSobolLdsWords - kRingDwords - kClassLdsMax / 4) / (int)(sizeof(CrtMaterial) / 4); }
 // The per-stage shade kernel of simple-material scenes without lights at infinity also runs four workgroups per CU
 // (128 registers, a 40 KB arena: cornellbox +2 %); the other instances spill too much at 128 registers (sun_sky -16 %).
@@ -520,6 +521,14 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend(
 // (cornellbox +1.3 %, MedCity +2 %, profiles/README.md). With lights present the strategy is checked at run time.
 // MATS: what the scene's material table holds — 0 simple (no coat, fuzz, thin film, transmission, subsurface anywhere:
 // the OpenPBR code is instantiated without those arms, shade.hip.h), 1 general, 2 general with interior media.
+// CRT_SHADE_STAMPS=1 builds (measurement only, never shipped): the four-wave shade kernels stamp the parts of their loop
+// with the cycle counter and sum wave cycles into Counters::cls_waves / cls_lanes, eight slots read and cleared by
+// crt_renderer_shade_class_stats. A load's wait is made explicit (vmcnt(0)) before its stamp, so the build is slower:
+// read ratios. shade_segment: [0] CLASSIFY load wait, [1] CLASSIFY work, [2] barriers, [3] vertex load wait,
+// [4] vertex compute, [5] stores, [6] iterations, [7] CLASSIFY rounds.
+#ifndef CRT_SHADE_STAMPS
+#define CRT_SHADE_STAMPS 0
+#endif
 template <int MATS, bool INF, bool LIT, int ARENA>
 __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                               const ShadowSoA &Q, Counters *C, int cur, float4 *staging,
@@ -581,12 +590,23 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
   __syncthreads();
   uint32_t next_in = 0;
   uint32_t head[kClasses], tail[kClasses];
+  constexpr bool STAMPS = CRT_SHADE_STAMPS != 0 && ARENA == kArenaWide;
+  unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = STAMPS ? __builtin_readcyclecounter() : 0ull;
+  auto lap = [&](int slot, bool drain) {
+    if (STAMPS) {
+      if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned long long t = __builtin_readcyclecounter();
+      t_acc[slot] += t - t0;
+      t0 = t;
+    }
+  };
 #pragma unroll
   for (int c = 0; c < kClasses; c++) head[c] = 0;
   for (;;) {
 #pragma unroll
     for (int c = 0; c < kClasses; c++) tail[c] = ring_tail[c];  // uniform: read between two barriers, nobody appends meanwhile
     __syncthreads();
+    lap(2, false);
     auto most_pending = [&](int &c_best) {
       uint32_t best = tail[0] - head[0];
       c_best = 0;
@@ -619,11 +639,13 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
         if (COMPACT && first && P.cam_compact) {  // uniform
           float4 a = S.a[i_c];
           asm volatile("" : "+v"(a.x));
+          if (STAMPS) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a.x) : : "memory");
           compact_camera_path(P, k_c, a, A, B, D);
         } else if (!(kRegenFirst && first)) {
           D = S.d[i_c]; A = S.a[i_c]; B = S.b[i_c];
           if (!first) Cc = S.c[i_c];
           asm volatile("" : "+v"(A.x), "+v"(B.x), "+v"(Cc.x));
+          if (STAMPS) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A.x), "+v"(D.x) : : "memory");
         } else {
           // a camera path: only the direction (escaped rays) and the film slot are needed here, and both follow from the
           // slot number; nothing of the path state is read (generate_segment)
@@ -635,6 +657,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
             D.y = cs.pix; D.w = cs.sl;
           }
         }
+        lap(0, false);
         const int remaining = (int)(D.z >> 16);
         const bool carries_medium = MEDIA && (D.w >> kMediumShift) != 0;
         if (!INF && hg == kInvalid && remaining > 0 && !carries_medium) {
@@ -668,10 +691,13 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
         const uint32_t at = seg_append(pending, &ring_tail[0]);
         if (pending) ring[at % kRing] = k_c;
       }
+      lap(1, false);
       __syncthreads();
 #pragma unroll
       for (int c = 0; c < kClasses; c++) tail[c] = ring_tail[c];
       __syncthreads();
+      lap(2, false);
+      if (STAMPS) t_acc[7]++;
     }
     const uint32_t avail = most_pending(c_sel);
     if (avail == 0) break;  // uniform: input exhausted and nothing pending
@@ -745,6 +771,8 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
         rec.p = ro + rd * rec.t;  // ray.at(t), rt_world.rs:221
       }
       hit_p = rec.p;
+      if (STAMPS) asm volatile("" : "+v"(hit_p.x), "+v"(beta.x), "+v"(L.x), "+v"(pattern));
+      lap(3, true);
 
       // bounce_emission_weight (tracer.rs:930-953). A previous bounce exists only where scatter returned a
       // sample, i.e. where eval is available, so the "eval is None" arm reduces to the delta flag.
@@ -893,6 +921,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
       }
     }
 
+    lap(4, false);
     // ---- wave-level compaction: survivors go to the other state buffer, finished paths to the film ----
     uint32_t j = 0;
     {
@@ -923,8 +952,13 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
       st_nt(&Q.b[q], make_float4(sh_d.x, sh_d.y, sh_d.z, time));
       st_nt(&Q.c[q], make_float4(sh_c.x, sh_c.y, sh_c.z, __uint_as_float(alive ? j : (kFilmTarget | film_idx))));
     }
+    lap(5, false);
     __syncthreads();  // every lane has read its ring entry before CLASSIFY appends again
+    lap(2, false);
+    if (STAMPS) t_acc[6]++;
   }
+  if (STAMPS && (threadIdx.x & 63) == 0)
+    for (int s = 0; s < 8; s++) atomicAdd(s < 4 ? &C->cls_waves[s] : &C->cls_lanes[s - 4], t_acc[s]);
   add_stat(&lds_ctr[2], s_closest); add_stat(&lds_ctr[3], s_shadow); add_stat(&lds_ctr[4], s_vertices);
   add_stat(&lds_ctr[5], s_rr_t); add_stat(&lds_ctr[6], s_rr_k); add_stat(&lds_ctr[7], s_esc);
   add_stat(&lds_ctr[8], s_depth);
@@ -946,6 +980,297 @@ __global__ __launch_bounds__(kBlock, WIDE ? CRT_SHADE_WIDE_WAVES : CRT_SHADE_WAV
   constexpr int ARENA = WIDE ? kArenaWide : kArenaDwords;
   __shared__ uint32_t sobol_tab[ARENA];
   shade_segment<MATS, INF, LIT, ARENA>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
+}
+
+// ---- shade, PIPELINED: the four-wave kernel of unlit simple-material scenes with one material class (cornellbox, the
+// bench) reads each path's state ONCE, and the reads of the next step travel while the current one computes. ----
+// shade_segment's iteration is a serial chain: CLASSIFY loads 68 bytes of every path and waits, two barriers, the vertex
+// step loads 84 bytes of every hit path AGAIN and waits, computes, stores. Nothing of step i + 1 is in flight while step
+// i computes, and the kernel has no registers left to hold it (121 of 128). Here
+//   * CLASSIFY reads the hit word only (4 bytes per path, requested one round ahead) and sorts slot numbers into two
+//     rings: hits and misses;
+//   * a STEP takes 256 entries of one ring — a vertex step (hits) or a miss step (escaped paths: sky, or the depth limit) —
+//     so both kinds run on full waves;
+//   * as soon as a wave has read the state of its current step out of its private LDS block it picks the entries of the
+//     NEXT step and requests their planes with global_load_lds_dwordx4: per-lane source address, no destination
+//     register, the block is written lane-linear (64 lanes x 16 bytes per plane). The loads are waited for (vmcnt) at the
+//     top of the next iteration, a whole vertex computation later.
+// Inside that span nothing may wait on the vector-memory counter early: the material table and the Sobol tables are read
+// through LDS pointers (ds_read, not FLAT loads, which count on vmcnt too), the barriers are raw s_barrier behind an
+// lgkmcnt wait (__syncthreads would drain vmcnt), and the only ordinary load — the next round's hit words — is used
+// after the wait at the top. Per-path arithmetic, film slots and counters are shade_segment's; only the order in which a
+// workgroup takes its paths differs, which no output depends on (the class rings and the lanes rely on the same).
+//
+// LDS budget of the pipelined instance (kArenaWide dwords): Sobol tables | material table | two rings | staging blocks.
+constexpr uint32_t kPipeRing = 2 * kBlock;             // entries per ring: < kBlock pending + one classify round
+constexpr int kPipePlanes = 5;                         // a b c d h, 1 KB per wave each, + 256 B of hit words
+constexpr int kPipeWaveDwords = kPipePlanes * 256 + 64;
+constexpr int kPipeStageDwords = (kBlock / 64) * kPipeWaveDwords;
+constexpr int kPipeRingDwords = 2 * (int)kPipeRing;
+constexpr int kMatDwords = (int)(sizeof(CrtMaterial) / 4);
+// The rule the host applies (Renderer::shade_pipe_fits): the pipelined instance runs only where the WHOLE material table
+// fits beside its staging blocks; every other scene keeps k_shade and its LDS-resident table. (A lit scene's plane e would
+// add 4 KB of staging and a partitioned scene's four rings 4 KB of rings: neither leaves room for a table.)
+constexpr int kPipeMatMax = (kArenaWide - kSobolLdsWords - kPipeRingDwords - kPipeStageDwords) / kMatDwords;
+static_assert(kPipeMatMax >= 6 && kSobolLdsWords + kPipeMatMax * kMatDwords + kPipeRingDwords + kPipeStageDwords <= kArenaWide,
+              "Sobol tables + material table + rings + staging blocks fit the four-wave arena");
+static_assert((kArenaWide - kPipeStageDwords) % 4 == 0 && kPipeWaveDwords % 4 == 0, "staging planes are 16-byte aligned");
+constexpr bool kShadePipeBuild = kBins == 1 && !kRegenFirst && CRT_SHADE_WIDE_WAVES == 4;
+#ifndef CRT_SHADE_PIPE_HIT_REGS
+#define CRT_SHADE_PIPE_HIT_REGS 0  // 1: the hit record of a vertex step by register loads at the top of the step, not staged (A/B)
+#endif
+
+typedef __attribute__((address_space(3))) void lds_void;
+__device__ __forceinline__ void lds_dma16(const void *src, uint32_t *lds_dst /* wave-uniform */) {
+  __builtin_amdgcn_global_load_lds(src, (lds_void *)lds_dst, 16, 0, 0);
+}
+__device__ __forceinline__ void lds_dma4(const void *src, uint32_t *lds_dst /* wave-uniform */) {
+  __builtin_amdgcn_global_load_lds(src, (lds_void *)lds_dst, 4, 0, 0);
+}
+// A workgroup barrier that orders LDS accesses only: loads into LDS that are in flight stay in flight.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// Stamps (CRT_SHADE_STAMPS): [0] waiting for the staged state, [1] classify rounds with their barriers, [2] picking and
+// requesting the next step, [3] vertex steps, [4] miss steps, [5] iterations, [6] rounds.
+__device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
+                                                   Counters *C, int cur, float4 *staging, uint32_t *arena /* kArenaWide */,
+                                                   bool first) {
+  constexpr bool STAMPS = CRT_SHADE_STAMPS != 0;
+  __shared__ uint32_t lds_ctr[10];   // [2..8] statistics
+  __shared__ uint32_t out_n;         // survivors
+  __shared__ uint32_t ring_tail[2];  // entries ever appended: hits, misses
+  const uint32_t n = uniform(((const volatile uint32_t *)C->seg[cur])[blockIdx.x]);
+  if (n == 0) {  // nothing lives in this segment: publish empty outputs and leave
+    if (threadIdx.x == 0) { C->seg[1 - cur][blockIdx.x] = 0; C->shadow[blockIdx.x] = 0; }
+    return;
+  }
+  if (threadIdx.x < 10) lds_ctr[threadIdx.x] = 0;
+  if (threadIdx.x == 0) out_n = 0;
+  if (threadIdx.x < 2) ring_tail[threadIdx.x] = 0;
+  sobol_tables_init(arena);  // ends with a workgroup barrier
+  // the material table, always in LDS here (kPipeMatMax) and read through an LDS pointer
+  uint32_t *mat_lds = arena + kSobolLdsWords;
+  {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(P.materials);
+    const uint32_t words = P.n_materials * (uint32_t)kMatDwords;
+    for (uint32_t w = threadIdx.x; w < words; w += kBlock) mat_lds[w] = src[w];
+  }
+  const CrtMaterial *mats = reinterpret_cast<const CrtMaterial *>(mat_lds);
+  uint32_t *ring_h = arena + kArenaWide - kPipeStageDwords - kPipeRingDwords, *ring_m = ring_h + kPipeRing;
+  uint32_t *stg = arena + kArenaWide - kPipeStageDwords + (threadIdx.x >> 6) * kPipeWaveDwords;  // this wave's block
+  const uint32_t lane = threadIdx.x & 63;
+  __syncthreads();
+  const uint32_t seg0 = blockIdx.x * P.seg_cap;  // kBins == 1: slot of the k-th live path = seg0 + k
+  const bool compact = CRT_CAM_COMPACT_BUILD && first && P.cam_compact;  // uniform: camera paths are plane a's 16 bytes
+  uint32_t s_closest = 0, s_vertices = 0, s_rr_t = 0, s_rr_k = 0, s_esc = 0, s_depth = 0;
+  unsigned long long t_acc[7] = {0, 0, 0, 0, 0, 0, 0}, t0 = 0;
+  auto lap = [&](int slot) {
+    if (STAMPS) { const unsigned long long t = __builtin_readcyclecounter(); t_acc[slot] += t - t0; t0 = t; }
+  };
+  uint32_t next_in = 0, head_h = 0, head_m = 0, tail_h = 0, tail_m = 0;  // uniform
+  uint32_t hg_next = threadIdx.x < n ? H.geom[seg0 + threadIdx.x] : kInvalid;  // the hit words of the next classify round
+  uint32_t kind = 0, take = 0, k_in = 0;  // the current step: 0 none yet, 1 vertex, 2 miss; its entries' states are on their way
+  if (STAMPS) t0 = __builtin_readcyclecounter();
+  for (;;) {
+    // ---- the current step's state: out of this wave's staging block, into registers ----
+    float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = make_float4(0.0f, 0.0f, 1.0f, 1.0f), Cc = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    float4 hh = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint4 D = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t hg = kInvalid;
+    if (kind) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's loads into its own block have landed
+      A = reinterpret_cast<const float4 *>(stg)[lane];
+      if (!compact) {
+        B = reinterpret_cast<const float4 *>(stg + 256)[lane];
+        D = reinterpret_cast<const uint4 *>(stg + 768)[lane];
+        if (!first) Cc = reinterpret_cast<const float4 *>(stg + 512)[lane];
+      }
+      if (kind == 1 && CRT_SHADE_PIPE_HIT_REGS) {
+        hh = H.h[seg0 + k_in];
+        hg = H.geom[seg0 + k_in];
+      } else if (kind == 1) {
+        hh = reinterpret_cast<const float4 *>(stg + 1024)[lane];
+        hg = stg[1280 + lane];
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ... and are in registers: the block may be overwritten
+    }
+    lap(0);
+    // ---- CLASSIFY rounds while both rings have room for one and input remains ----
+    while (next_in < n && tail_h - head_h < (uint32_t)kBlock && tail_m - head_m < (uint32_t)kBlock) {
+      lds_barrier();  // every wave has read the ring entries and the tails of the round before
+      const uint32_t k_c = next_in + threadIdx.x;
+      const uint32_t hg_c = hg_next;
+      next_in += kBlock;
+      hg_next = kInvalid;
+      if (next_in + threadIdx.x < n) hg_next = H.geom[seg0 + next_in + threadIdx.x];
+      const bool hit = k_c < n && hg_c != kInvalid, miss = k_c < n && hg_c == kInvalid;
+      const uint32_t at_h = seg_append(hit, &ring_tail[0]);
+      if (hit) ring_h[at_h % kPipeRing] = k_c;
+      const uint32_t at_m = seg_append(miss, &ring_tail[1]);
+      if (miss) ring_m[at_m % kPipeRing] = k_c;
+      lds_barrier();
+      tail_h = uniform(ring_tail[0]);
+      tail_m = uniform(ring_tail[1]);
+      if (STAMPS) t_acc[6]++;
+    }
+    lap(1);
+    // ---- the next step: a workgroup's worth of hits, else of misses, else (input exhausted) what is left ----
+    const uint32_t pend_h = tail_h - head_h, pend_m = tail_m - head_m;
+    uint32_t kind_n = 0, take_n = 0, k_n = 0;
+    if (pend_h >= (uint32_t)kBlock || (pend_h && pend_m < (uint32_t)kBlock)) { kind_n = 1; take_n = pend_h < (uint32_t)kBlock ? pend_h : (uint32_t)kBlock; }
+    else if (pend_m) { kind_n = 2; take_n = pend_m < (uint32_t)kBlock ? pend_m : (uint32_t)kBlock; }
+    if (kind_n && threadIdx.x < take_n) {
+      k_n = kind_n == 1 ? ring_h[(head_h + threadIdx.x) % kPipeRing] : ring_m[(head_m + threadIdx.x) % kPipeRing];
+      const uint32_t i_n = seg0 + k_n;
+      lds_dma16(&S.a[i_n], stg);
+      if (!compact) {
+        lds_dma16(&S.b[i_n], stg + 256);
+        lds_dma16(&S.d[i_n], stg + 768);
+        if (!first) lds_dma16(&S.c[i_n], stg + 512);
+      }
+      if (kind_n == 1 && !CRT_SHADE_PIPE_HIT_REGS) {
+        lds_dma16(&H.h[i_n], stg + 1024);
+        lds_dma4(&H.geom[i_n], stg + 1280);
+      }
+    }
+    head_h += kind_n == 1 ? take_n : 0u;
+    head_m += kind_n == 2 ? take_n : 0u;
+    lap(2);
+    const bool active = threadIdx.x < take;
+    if (kind == 2) {
+      // ---- MISS step (tracer.rs:1321-1342, :1123-1149): the path ends on the sky gradient, or at the depth limit ----
+      if (active) {
+        if (compact) compact_camera_path(P, k_in, A, A, B, D);
+        const int remaining = (int)(D.z >> 16);
+        const V3 rd = v3(A.w, B.x, B.y), beta = v3(B.z, B.w, Cc.x);
+        V3 L = v3(Cc.y, Cc.z, Cc.w);
+        if (remaining > 0) {
+          s_closest++;
+          s_esc++;
+          const V3 unit_direction = normalize(rd);
+          const V3 background = splat(0.0f) + sky_gradient(unit_direction);
+          L = L + beta * background;
+        } else {  // depth exhausted: nothing is added
+          s_depth++;
+          if ((D.w & kPrevValid) != 0) s_closest++;
+        }
+        st_nt(&staging[(D.w & 0xffffu) * P.n_act + D.y], make_float4(L.x, L.y, L.z, 0.0f));
+      }
+      lap(4);
+    } else if (kind == 1) {
+      // ---- VERTEX step: shade_segment's, for a hit on a simple material in a scene without lights or media ----
+      bool alive = false;
+      V3 L = splat(0.0f), beta = splat(1.0f), n_o = splat(0.0f), n_d = splat(0.0f);
+      uint32_t meta = 0, aux = 0, pix = 0, pattern = 0;
+      bool n_delta = false;
+      if (active) {
+        if (compact) compact_camera_path(P, k_in, A, A, B, D);
+        const V3 ro = v3(A.x, A.y, A.z), rd = v3(A.w, B.x, B.y);
+        beta = v3(B.z, B.w, Cc.x);
+        L = v3(Cc.y, Cc.z, Cc.w);
+        pattern = D.x; pix = D.y; meta = D.z; aux = D.w;
+        const uint32_t n_rec = meta & 0xffffu;
+        const int remaining = (int)(meta >> 16);
+        const bool prev_valid = (aux & kPrevValid) != 0;
+        const uint32_t mat_i = hg & 0x7fffffffu;  // the material record's index: the geometry id
+        HitRec rec;
+        rec.front_face = ((hg >> 31) & 1u) != 0;
+        rec.t = hh.x;
+        rec.normal = v3(hh.y, hh.z, hh.w);
+        rec.p = ro + rd * rec.t;  // ray.at(t), rt_world.rs:221
+        const CrtMaterial &mat = mats[mat_i];
+        const float emission_weight = 1.0f;  // bounce_emission_weight without lights (tracer.rs:930-953)
+        if (remaining <= 0) {  // tracer.rs:1123-1149: depth exhausted, last-vertex emission only
+          s_depth++;
+          if (prev_valid) {
+            s_closest++;
+            const float cos_o = fabs_(dot(normalize(rd), rec.normal));
+            const V3 emitted = mat_emitted_directional<true>(mat, cos_o);
+            if (len2(emitted) > 0.0f) L = L + beta * (emitted * emission_weight);
+          }
+        } else {
+          s_closest++;
+          const Sampler vdom = new_domain(Sampler{pattern, P.sample_begin + (aux & 0xffffu)}, (int)n_rec);  // :1121
+          const V3 atten = splat(1.0f);
+          const float cos_o = fabs_(dot(normalize(rd), rec.normal));
+          const V3 emitted = mat_emitted_directional<true>(mat, cos_o);
+          V3 emit_here = splat(0.0f);
+          if (prev_valid) {  // tracer.rs:1372-1381
+            if (len2(emitted) > 0.0f) L = L + beta * ((atten * emitted) * emission_weight);
+          } else {
+            emit_here = emitted;
+          }
+          const V3 ba = beta * atten;
+          L = L + ba * emit_here;
+          // indirect lighting by BSDF sampling (tracer.rs:1459-1523)
+          Scatter sample;
+          if (mat_scatter<true>(mat, rd, rec, new_domain(vdom, K_BSDF), sample, arena)) {
+            const V3 dir = normalize(sample.dir);
+            const float cosine = sample.delta ? 1.0f : fabs_(dot(rec.normal, dir));
+            const V3 factor = (sample.value * cosine) / sample.pdf;
+            beta = beta * (atten * factor);
+            bool survived = true;
+            if (n_rec >= (uint32_t)kRrStartBounce) {
+              s_rr_t++;
+              const float p_survive = rclamp(max_elem(beta), kRrMinProb, 1.0f);
+              if (p_survive < 1.0f) {
+                if (draw_rnd1(new_domain(vdom, K_RR)) >= p_survive) {
+                  survived = false;
+                  s_rr_k++;
+                } else {
+                  beta = beta / p_survive;
+                }
+              }
+            }
+            if (survived) {
+              alive = true;
+              n_o = sample.origin; n_d = sample.dir; n_delta = sample.delta;
+            }
+          }
+          s_vertices++;
+        }
+      }
+      // survivors go to the other state buffer, finished paths to the film
+      const uint32_t j = seg0 + seg_append(alive, &out_n);
+      const uint32_t sl = aux & 0xffffu;
+      if (alive) {
+        st_nt(&N.a[j], make_float4(n_o.x, n_o.y, n_o.z, n_d.x));
+        st_nt(&N.b[j], make_float4(n_d.y, n_d.z, beta.x, beta.y));
+        st_nt(&N.c[j], make_float4(beta.z, L.x, L.y, L.z));
+        st_nt(&N.d[j], make_uint4(pattern, pix, ((meta & 0xffffu) + 1u) | (((meta >> 16) - 1u) << 16),
+                                  sl | kPrevValid | (n_delta ? kPrevDelta : 0u)));
+      } else if (active) {
+        st_nt(&staging[sl * P.n_act + pix], make_float4(L.x, L.y, L.z, 0.0f));
+      }
+      lap(3);
+    }
+    if (STAMPS) t_acc[5]++;
+    if (!kind_n) break;  // uniform: input exhausted and nothing pending
+    kind = kind_n; take = take_n; k_in = k_n;
+  }
+  add_stat(&lds_ctr[2], s_closest); add_stat(&lds_ctr[4], s_vertices);
+  add_stat(&lds_ctr[5], s_rr_t); add_stat(&lds_ctr[6], s_rr_k); add_stat(&lds_ctr[7], s_esc);
+  add_stat(&lds_ctr[8], s_depth);
+  __syncthreads();
+  if (threadIdx.x == 0) {  // publish this segment's queues for the next stages (same workgroup index there)
+    C->shadow[blockIdx.x] = 0;
+    C->seg[1 - cur][blockIdx.x] = out_n;
+    C->seg[cur][blockIdx.x] = 0;  // consumed: this buffer is the output of the next round
+  }
+  if (threadIdx.x >= 1 && threadIdx.x <= 7 && lds_ctr[threadIdx.x + 1])
+    atomicAdd(&C->stats[threadIdx.x], (unsigned long long)lds_ctr[threadIdx.x + 1]);
+  if (STAMPS && lane == 0)
+    for (int s = 0; s < 7; s++) atomicAdd(s < 4 ? &C->cls_waves[s] : &C->cls_lanes[s - 4], t_acc[s]);
+}
+__global__ __launch_bounds__(kBlock, CRT_SHADE_WIDE_WAVES) void k_shade_pipe(Params P, PathSoA S, PathSoA N, HitSoA H, Counters *C,
+                                                                              int cur, float4 *staging, int first) {
+  __shared__ __attribute__((aligned(16))) uint32_t arena[kArenaWide];
+  shade_segment_pipe(P, S, N, H, C, cur, staging, arena, first != 0);
 }
 
 // ---- shadow: World::occluded (rt_world.rs:235-237) for the queue; unoccluded requests pay out ----
@@ -1179,6 +1504,14 @@ struct Renderer {
   size_t max_batch_slots = 0;     // CRT_MAX_BATCH_SLOTS (tests): ensure_buffers fails above this many slots; 0 = no limit
   int tail_from = 12;             // CRT_TAIL_FROM: the bounce from which a per-stage batch finishes in one fused launch
   int noclassify_from = 1 << 30;  // CRT_NOCLASSIFY_FROM: per-stage shade without its CLASSIFY pass from this bounce on
+  int shade_pipe = 1;             // CRT_SHADE_PIPE: 0 = never the pipelined four-wave shade kernel (A/B, tests)
+  bool shade_piped = false;       // the LAST batch ran it (crt_renderer_pipeline)
+  // The pipelined shade kernel serves unlit simple-material scenes of one material class whose whole material table fits
+  // the arena beside the staging blocks (kPipeMatMax); every other scene keeps k_shade with its LDS-resident table.
+  bool shade_pipe_fits() const {
+    return kShadePipeBuild && shade_pipe != 0 && mats_kind == 0 && P.n_lights == 0 && !P.has_motion && !P.mat_index &&
+           P.partition == 0 && !P.class_stats && P.n_materials <= (uint32_t)kPipeMatMax;
+  }
   int force_fused = -1;    // CRT_FUSED: -1 unset
   size_t stage_min_paths = (size_t)96 << 20;  // cornellbox 1080p, fused / per-stage Mray/s: 66 M paths 7507 / 7300, 133 M 7658 / 7900
   bool fused = true;       // what the LAST batch ran (crt_renderer_pipeline)
@@ -1389,6 +1722,7 @@ struct Renderer {
     p.n_act = adaptive ? n_act : P.n_pix;
     p.active = (adaptive && n_act < P.n_pix) ? d_active : nullptr;
     if (const int rc = plan_lane(B, p, n_samples, d_tstats)) return rc;
+    shade_piped = false;
     float4 *staging = B.staging;
     const bool wide = !fused && this->wide;  // per-stage launches take the scene's preferred traversal kernels
     const bool wdirect = wide && engine.wide_direct && CRT_WIDE_DIRECT_BUILD != 0;  // ... their direct-engine instances
@@ -1504,7 +1838,14 @@ struct Renderer {
       if (mats_kind == 2) { if (P.has_inf_lights) CRT_SHADE(2, true, false, true); else if (lit) CRT_SHADE(2, false, false, true); else CRT_SHADE(2, false, false, false); }
       else if (mats_kind == 1) { if (P.has_inf_lights) CRT_SHADE(1, true, false, true); else if (lit) CRT_SHADE(1, false, false, true); else CRT_SHADE(1, false, false, false); }
       else if (P.has_inf_lights) CRT_SHADE(0, true, false, true);
-      else if (wide && !P.mat_index && shade_wide != 0) { if (lit) CRT_SHADE(0, false, true, true); else CRT_SHADE(0, false, true, false); }
+      else if (wide && !P.mat_index && shade_wide != 0) {
+        if (lit) CRT_SHADE(0, false, true, true);
+        else if (shade_pipe_fits() && (int)it < noclassify_from) {  // the pipelined instance (shade_segment_pipe)
+          shade_piped = true;
+          timed(1, st, [&] { hipLaunchKernelGGL(k_shade_pipe, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, it == 0 ? 1 : 0); });
+        }
+        else CRT_SHADE(0, false, true, false);
+      }
       else { if (lit) CRT_SHADE(0, false, false, true); else CRT_SHADE(0, false, false, false); }
 #undef CRT_SHADE
       if (P.n_lights > 0 && P.strategy != CRT_STRATEGY_BSDF) {
@@ -1704,6 +2045,7 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   if (knobs.prefer_stage >= 0) r.prefer_stage = knobs.prefer_stage != 0;  // the A/B knobs (crt_internal.h, Knobs): CRT_PREFER_STAGE ...
   r.cam_compact_ok = knobs.cam_compact != 0;
   r.noclassify_from = knobs.noclassify_from;
+  r.shade_pipe = knobs.shade_pipe;
   r.tail_from = knobs.tail_from;
   r.max_batch_slots = knobs.max_batch_slots;
   r.n_lanes = knobs.lanes < 1 ? 1 : (knobs.lanes > Renderer::kMaxLanes ? Renderer::kMaxLanes : knobs.lanes);
@@ -1844,7 +2186,7 @@ int crt_renderer_set_lanes(CrtRenderer *r, int lanes) {
 int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   if (!r || !out) return CRT_ERR_BAD_ARG;
   out[0] = r->r.fused ? 1u : 0u;
-  out[1] = (!r->r.fused && r->r.wide) ? 1u : 0u;
+  out[1] = ((!r->r.fused && r->r.wide) ? 1u : 0u) | ((!r->r.fused && r->r.shade_piped) ? 2u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }
