@@ -307,6 +307,7 @@ struct Knobs {
   int wide = -1;              // CRT_WIDE
   // renderer
   int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, shade_wide = -1, shade_pipe = 1, fused = -1;
+  int mat_derived = 1;        // CRT_MAT_DERIVED: 0 = the shade kernels compute the per-material constants at every vertex again
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
 };

@@ -170,6 +170,10 @@ struct Params {
   DevScene scene;
   uint32_t sample_begin;
   const CrtMaterial *materials;
+  // One DevMaterial per record of `materials`: the per-material constants of the vertex code, derived once
+  // (k_derive_materials). The DERIVED kernel instances stage and read this table and go back to `materials` only in the
+  // arms shade.hip.h names; CRT_MAT_DERIVED=0 launches the instances that read `materials` alone.
+  const DevMaterial *mat_derived;
   uint32_t n_materials;
   // geom_id -> record of `materials` (and of `media`, `mat_class`), or nullptr: the table is indexed by geom_id itself.
   // World::attach binds a material per geometry (rt_world.rs:111-122) and an instanced city binds the same few looks
@@ -289,6 +293,27 @@ __global__ void k_build_media(const CrtMaterial *materials, uint32_t n, DevMediu
   m.id = 0;
   media[i] = m;
 }
+// ---- the per-material constants of the vertex code (shade.hip.h, DevMaterial), derived once per renderer with the
+// inline functions the vertex code itself runs on a raw record: the same operations, so the same bits. ----
+__global__ void k_derive_materials(const CrtMaterial *materials, uint32_t n, DevMaterial *derived) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  DevMaterial d;
+  derive_material(materials[i], d);
+  derived[i] = d;
+}
+// The table a shade instance stages and indexes, and its view of record i.
+template <bool DRV> struct MatTable;
+template <> struct MatTable<false> {
+  typedef CrtMaterial Rec;
+  __device__ __forceinline__ static const Rec *of(const Params &P) { return P.materials; }
+  __device__ __forceinline__ static MatRaw view(const Rec *table, const Params &, uint32_t i) { return MatRaw{table[i]}; }
+};
+template <> struct MatTable<true> {
+  typedef DevMaterial Rec;
+  __device__ __forceinline__ static const Rec *of(const Params &P) { return P.mat_derived; }
+  __device__ __forceinline__ static MatDerived view(const Rec *table, const Params &P, uint32_t i) { return MatDerived{table[i], P.materials[i]}; }
+};
 constexpr int kNumberBlock = 1024;
 __global__ __launch_bounds__(kNumberBlock) void k_number_media(uint32_t n, DevMedium *media, DevMedium *by_id, uint32_t *count_out) {
   __shared__ uint32_t run_sum[kNumberBlock];
@@ -529,13 +554,15 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend(
 #ifndef CRT_SHADE_STAMPS
 #define CRT_SHADE_STAMPS 0
 #endif
-template <int MATS, bool INF, bool LIT, int ARENA>
+template <int MATS, bool INF, bool LIT, int ARENA, bool DRV>
 __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                               const ShadowSoA &Q, Counters *C, int cur, float4 *staging,
                                               uint32_t *sobol_tab /* ARENA dwords: Sobol tables, then the material table */,
                                               bool first /* camera paths whose plane c was not written (generate_segment) */,
                                               bool all_pending = false /* no CLASSIFY pass: every path takes the vertex step */) {
   constexpr bool MEDIA = MATS == 2, SIMPLE = MATS == 0;
+  static_assert(SIMPLE || !DRV, "the derived record covers what a simple-material table reads (shade.hip.h)");
+  typedef MatTable<DRV> Table;
   // Two of round 3's forms are compiled only into the instances that have registers to spare: the lit four-wave shade
   // kernel sits at its 128-register limit with 17 spilled, and the few branches of either form cost it 3.6 % / 0.9 %
   // (cornellbox_guided) where the unlit one gains 1 % (profiles/README.md). The host sets Params::cam_compact for
@@ -558,13 +585,14 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
   // The vertex code reads its material record a field at a time, where each lobe needs it: two dozen dependent
   // round trips to L2 per vertex. A table that fits the rest of the arena is staged in LDS once per call instead
   // (generic pointer: the reads become FLAT loads served by LDS); larger tables stay in global memory.
-  const CrtMaterial *mats = P.materials;
+  // (Either table: a DevMaterial has the size of a CrtMaterial, so mat_lds_max holds for both.)
+  const typename Table::Rec *mats = Table::of(P);
   if (P.n_materials <= (uint32_t)mat_lds_max(ARENA)) {
     uint32_t *dst = sobol_tab + kSobolLdsWords;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(P.materials);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(mats);
     const uint32_t words = P.n_materials * (uint32_t)(sizeof(CrtMaterial) / 4);
     for (uint32_t w = threadIdx.x; w < words; w += kBlock) dst[w] = src[w];
-    mats = reinterpret_cast<const CrtMaterial *>(dst);
+    mats = reinterpret_cast<const typename Table::Rec *>(dst);
     __syncthreads();
   }
   const uint32_t seg0 = blockIdx.x * P.seg_cap;  // shadow queue: one unbinned segment per workgroup
@@ -794,7 +822,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
         if (prev_valid) {
           s_closest++;
           if (has_hit) {
-            const CrtMaterial &mat = mats[mat_i];
+            const auto mat = Table::view(mats, P, mat_i);
             const float cos_o = fabs_(dot(normalize(rd), rec.normal));
             V3 emitted = mat_emitted_directional<SIMPLE>(mat, cos_o);
             if (len2(emitted) > 0.0f) {
@@ -846,7 +874,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
                                     : splat(0.0f) + sky_gradient(unit_direction);
           L = L + beta * background;
         } else {
-          const CrtMaterial &mat = mats[mat_i];
+          const auto mat = Table::view(mats, P, mat_i);
           // tracer.rs:1352-1361: a scattering medium already paid e^{-sigma_bar t} through the free-flight
           // competition, only the chromatic correction remains; a clear one keeps pure Beer-Lambert.
           V3 atten = splat(1.0f);
@@ -973,13 +1001,13 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
   if (threadIdx.x >= 1 && threadIdx.x <= 7 && lds_ctr[threadIdx.x + 1])
     atomicAdd(&C->stats[threadIdx.x], (unsigned long long)lds_ctr[threadIdx.x + 1]);
 }
-template <int MATS, bool INF, bool WIDE, bool LIT>
+template <int MATS, bool INF, bool WIDE, bool LIT, bool DRV>
 __global__ __launch_bounds__(kBlock, WIDE ? CRT_SHADE_WIDE_WAVES : CRT_SHADE_WAVES) void k_shade(Params P, PathSoA S, PathSoA N, HitSoA H, ShadowSoA Q,
                                                                    Counters *C, int cur, float4 *staging, int first) {
   static_assert(LIT || !INF, "lights at infinity are lights");
   constexpr int ARENA = WIDE ? kArenaWide : kArenaDwords;
   __shared__ uint32_t sobol_tab[ARENA];
-  shade_segment<MATS, INF, LIT, ARENA>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
+  shade_segment<MATS, INF, LIT, ARENA, DRV>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
 }
 
 // ---- shade, PIPELINED: the four-wave kernel of unlit simple-material scenes with one material class (cornellbox, the
@@ -1037,6 +1065,7 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 
 // Stamps (CRT_SHADE_STAMPS): [0] waiting for the staged state, [1] classify rounds with their barriers, [2] picking and
 // requesting the next step, [3] vertex steps, [4] miss steps, [5] iterations, [6] rounds.
+template <bool DRV>
 __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                                    Counters *C, int cur, float4 *staging, uint32_t *arena /* kArenaWide */,
                                                    bool first) {
@@ -1056,11 +1085,11 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
   // the material table, always in LDS here (kPipeMatMax) and read through an LDS pointer
   uint32_t *mat_lds = arena + kSobolLdsWords;
   {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(P.materials);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(MatTable<DRV>::of(P));
     const uint32_t words = P.n_materials * (uint32_t)kMatDwords;
     for (uint32_t w = threadIdx.x; w < words; w += kBlock) mat_lds[w] = src[w];
   }
-  const CrtMaterial *mats = reinterpret_cast<const CrtMaterial *>(mat_lds);
+  const typename MatTable<DRV>::Rec *mats = reinterpret_cast<const typename MatTable<DRV>::Rec *>(mat_lds);
   uint32_t *ring_h = arena + kArenaWide - kPipeStageDwords - kPipeRingDwords, *ring_m = ring_h + kPipeRing;
   uint32_t *stg = arena + kArenaWide - kPipeStageDwords + (threadIdx.x >> 6) * kPipeWaveDwords;  // this wave's block
   const uint32_t lane = threadIdx.x & 63;
@@ -1183,7 +1212,7 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
         rec.t = hh.x;
         rec.normal = v3(hh.y, hh.z, hh.w);
         rec.p = ro + rd * rec.t;  // ray.at(t), rt_world.rs:221
-        const CrtMaterial &mat = mats[mat_i];
+        const auto mat = MatTable<DRV>::view(mats, P, mat_i);
         const float emission_weight = 1.0f;  // bounce_emission_weight without lights (tracer.rs:930-953)
         if (remaining <= 0) {  // tracer.rs:1123-1149: depth exhausted, last-vertex emission only
           s_depth++;
@@ -1267,10 +1296,11 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
   if (STAMPS && lane == 0)
     for (int s = 0; s < 7; s++) atomicAdd(s < 4 ? &C->cls_waves[s] : &C->cls_lanes[s - 4], t_acc[s]);
 }
+template <bool DRV>
 __global__ __launch_bounds__(kBlock, CRT_SHADE_WIDE_WAVES) void k_shade_pipe(Params P, PathSoA S, PathSoA N, HitSoA H, Counters *C,
                                                                               int cur, float4 *staging, int first) {
   __shared__ __attribute__((aligned(16))) uint32_t arena[kArenaWide];
-  shade_segment_pipe(P, S, N, H, C, cur, staging, arena, first != 0);
+  shade_segment_pipe<DRV>(P, S, N, H, C, cur, staging, arena, first != 0);
 }
 
 // ---- shadow: World::occluded (rt_world.rs:235-237) for the queue; unoccluded requests pay out ----
@@ -1329,7 +1359,7 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_SHADOW_WAVES) void k_shadow(
 // this code base ever showed — round 2, run-to-run differences of a few ulps — was confined to k_path<., LIT, INF> of
 // one build, whose per-stage launches of the same shade code were exact; its cause was never established
 // (profiles/README.md, "The round-2 nondeterminism"), so that kernel family is not built.
-template <int MATS, bool LIT, int COLD>
+template <int MATS, bool LIT, int COLD, bool DRV>
 __global__ __launch_bounds__(kBlock, CRT_EXTEND_WAVES) void k_path(Params P, PathSoA S0, PathSoA S1, HitSoA H, ShadowSoA Q, Counters *C,
                                                  float4 *staging, uint32_t sample_begin, uint32_t n_samples,
                                                  uint32_t start_it, int cur0) {
@@ -1347,7 +1377,7 @@ __global__ __launch_bounds__(kBlock, CRT_EXTEND_WAVES) void k_path(Params P, Pat
     const PathSoA &N = cur ? S0 : S1;
     extend_segment<false, false, COLD, false>(P, S, H, C, cur, it == 0 ? 1 : 0, nullptr, arena);
     __syncthreads();  // hit records of this segment are complete; the arena changes hands
-    shade_segment<MATS, false, LIT, kArenaDwords>(P, S, N, H, Q, C, cur, staging, arena, false);
+    shade_segment<MATS, false, LIT, kArenaDwords, DRV>(P, S, N, H, Q, C, cur, staging, arena, false);
     __syncthreads();
     if (LIT) {
       shadow_segment<false, false>(P, N, Q, C, staging, nullptr, arena);
@@ -1477,6 +1507,8 @@ struct Renderer {
   hipEvent_t ev_start = nullptr;
   float4 *film = nullptr;
   CrtMaterial *d_materials = nullptr;
+  DevMaterial *d_mat_derived = nullptr;  // one per record of d_materials (k_derive_materials)
+  bool mat_derived = true;         // CRT_MAT_DERIVED: simple-material scenes launch the instances that read it
   uint8_t *d_mat_class = nullptr;  // material_class() per record of d_materials
   uint16_t *d_mat_index = nullptr; // geom_id -> record, when the table is deduplicated (Params::mat_index)
   DevMedium *d_media = nullptr;  // [n_materials] by geom_id, then [n_materials] by compact id
@@ -1538,6 +1570,7 @@ struct Renderer {
     if (ev_start) (void)hipEventDestroy(ev_start);
     if (film) (void)hipFree(film);
     if (d_materials) (void)hipFree(d_materials);
+    if (d_mat_derived) (void)hipFree(d_mat_derived);
     if (d_mat_class) (void)hipFree(d_mat_class);
     if (d_mat_index) (void)hipFree(d_mat_index);
     if (d_media) (void)hipFree(d_media);
@@ -1749,6 +1782,7 @@ struct Renderer {
       return CRT_OK;
     };
     const bool lit = P.n_lights > 0;  // the kernel instance; whether the strategy samples the lights is checked in shade
+    const bool drv = mats_kind == 0 && mat_derived;  // simple-material tables read the derived records (CRT_MAT_DERIVED=0: never)
     // the cold per-ray state the scene can need (DevScene::cold) picks the closest-hit kernels' instance: none / the
     // pending normal only / everything for the per-stage k_extend, none / everything for the fused kernel of simple
     // scenes — decided by select_engine, with the image in hand; a launch the image cannot take is refused, never made
@@ -1770,22 +1804,31 @@ struct Renderer {
     }
     if (fused) {  // one launch for the whole path loop (class 0 of the profile), then the film fold
       timed(0, st, [&] {
-#define CRT_PATH(M, L, CO) \
-  hipLaunchKernelGGL((k_path<M, L, CO>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0)
+#define CRT_PATH(M, L, CO) CRT_PATH_D(M, L, CO, false)
+#define CRT_PATH_D(M, L, CO, D) \
+  hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0)
 #if CRT_NOPK_BUILD  // the packet-free instances exist only in builds that ask for them (A/B: profiles/README.md, round 4)
 #define CRT_PATH_NP(M, L) do { if (nopk) CRT_PATH(M, L, kColdAll | kNoPackets); else CRT_PATH(M, L, kColdAll); } while (0)
 #else
 #define CRT_PATH_NP(M, L) CRT_PATH(M, L, kColdAll)
 #endif
         switch (mats_kind * 2 + (lit ? 1 : 0)) {
-          case 0: if (path_cold == 0) CRT_PATH(0, false, 0); else CRT_PATH(0, false, kColdAll); break;
-          case 1: if (path_cold == 0) CRT_PATH(0, true, 0); else CRT_PATH(0, true, kColdAll); break;
+          // simple-material tables: the instances that read the derived records (drv), or the raw ones (CRT_MAT_DERIVED=0)
+          case 0:
+            if (drv) { if (path_cold == 0) CRT_PATH_D(0, false, 0, true); else CRT_PATH_D(0, false, kColdAll, true); }
+            else { if (path_cold == 0) CRT_PATH(0, false, 0); else CRT_PATH(0, false, kColdAll); }
+            break;
+          case 1:
+            if (drv) { if (path_cold == 0) CRT_PATH_D(0, true, 0, true); else CRT_PATH_D(0, true, kColdAll, true); }
+            else { if (path_cold == 0) CRT_PATH(0, true, 0); else CRT_PATH(0, true, kColdAll); }
+            break;
           case 2: CRT_PATH_NP(1, false); break;
           case 3: CRT_PATH_NP(1, true); break;
           case 4: CRT_PATH_NP(2, false); break;
           default: CRT_PATH_NP(2, true); break;
         }
 #undef CRT_PATH_NP
+#undef CRT_PATH_D
 #undef CRT_PATH
       });
       return fold();
@@ -1801,22 +1844,30 @@ struct Renderer {
     for (uint32_t it = 0; it <= P.max_depth; it++) {
       if (it >= tail_at) {
         timed(3, st, [&] {
-#define CRT_TAIL(M, L, CO) \
-  hipLaunchKernelGGL((k_path<M, L, CO>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, it, cur)
+#define CRT_TAIL(M, L, CO) CRT_TAIL_D(M, L, CO, false)
+#define CRT_TAIL_D(M, L, CO, D) \
+  hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, it, cur)
 #if CRT_NOPK_BUILD
 #define CRT_TAIL_NP(M, L) do { if (nopk) CRT_TAIL(M, L, kColdAll | kNoPackets); else CRT_TAIL(M, L, kColdAll); } while (0)
 #else
 #define CRT_TAIL_NP(M, L) CRT_TAIL(M, L, kColdAll)
 #endif
           switch (mats_kind * 2 + (lit ? 1 : 0)) {
-            case 0: if (path_cold == 0) CRT_TAIL(0, false, 0); else CRT_TAIL(0, false, kColdAll); break;
-            case 1: if (path_cold == 0) CRT_TAIL(0, true, 0); else CRT_TAIL(0, true, kColdAll); break;
+            case 0:
+              if (drv) { if (path_cold == 0) CRT_TAIL_D(0, false, 0, true); else CRT_TAIL_D(0, false, kColdAll, true); }
+              else { if (path_cold == 0) CRT_TAIL(0, false, 0); else CRT_TAIL(0, false, kColdAll); }
+              break;
+            case 1:
+              if (drv) { if (path_cold == 0) CRT_TAIL_D(0, true, 0, true); else CRT_TAIL_D(0, true, kColdAll, true); }
+              else { if (path_cold == 0) CRT_TAIL(0, true, 0); else CRT_TAIL(0, true, kColdAll); }
+              break;
             case 2: CRT_TAIL_NP(1, false); break;
             case 3: CRT_TAIL_NP(1, true); break;
             case 4: CRT_TAIL_NP(2, false); break;
             default: CRT_TAIL_NP(2, true); break;
           }
 #undef CRT_TAIL_NP
+#undef CRT_TAIL_D
 #undef CRT_TAIL
         });
         break;
@@ -1831,22 +1882,29 @@ struct Renderer {
       else if (wide) { if (ext_cold == 0) CRT_EXTEND(false, 1, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 1, kColdNormal); else CRT_EXTEND(false, 1, kColdAll); }
       else { if (ext_cold == 0) CRT_EXTEND(false, 0, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 0, kColdNormal); else CRT_EXTEND(false, 0, kColdAll); }
 #undef CRT_EXTEND
-#define CRT_SHADE(M, I, W, L) \
-  timed(1, st, [&] { hipLaunchKernelGGL((k_shade<M, I, W, L>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (it == 0 ? 1 : 0) | ((int)it >= noclassify_from ? 2 : 0)); })
+#define CRT_SHADE(M, I, W, L) CRT_SHADE_D(M, I, W, L, false)
+#define CRT_SHADE0(I, W, L) do { if (drv) CRT_SHADE_D(0, I, W, L, true); else CRT_SHADE_D(0, I, W, L, false); } while (0)
+#define CRT_SHADE_D(M, I, W, L, D) \
+  timed(1, st, [&] { hipLaunchKernelGGL((k_shade<M, I, W, L, D>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (it == 0 ? 1 : 0) | ((int)it >= noclassify_from ? 2 : 0)); })
       // the instance: material table (MATS), lights at infinity (INF), four waves (simple materials without lights at
       // infinity, when the scene runs the wide kernels), and — as for k_path — whether the light list is empty
       if (mats_kind == 2) { if (P.has_inf_lights) CRT_SHADE(2, true, false, true); else if (lit) CRT_SHADE(2, false, false, true); else CRT_SHADE(2, false, false, false); }
       else if (mats_kind == 1) { if (P.has_inf_lights) CRT_SHADE(1, true, false, true); else if (lit) CRT_SHADE(1, false, false, true); else CRT_SHADE(1, false, false, false); }
-      else if (P.has_inf_lights) CRT_SHADE(0, true, false, true);
+      else if (P.has_inf_lights) CRT_SHADE0(true, false, true);
       else if (wide && !P.mat_index && shade_wide != 0) {
-        if (lit) CRT_SHADE(0, false, true, true);
+        if (lit) CRT_SHADE0(false, true, true);
         else if (shade_pipe_fits() && (int)it < noclassify_from) {  // the pipelined instance (shade_segment_pipe)
           shade_piped = true;
-          timed(1, st, [&] { hipLaunchKernelGGL(k_shade_pipe, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, it == 0 ? 1 : 0); });
+          timed(1, st, [&] {
+            if (drv) hipLaunchKernelGGL(k_shade_pipe<true>, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, it == 0 ? 1 : 0);
+            else hipLaunchKernelGGL(k_shade_pipe<false>, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, it == 0 ? 1 : 0);
+          });
         }
-        else CRT_SHADE(0, false, true, false);
+        else CRT_SHADE0(false, true, false);
       }
-      else { if (lit) CRT_SHADE(0, false, false, true); else CRT_SHADE(0, false, false, false); }
+      else { if (lit) CRT_SHADE0(false, false, true); else CRT_SHADE0(false, false, false); }
+#undef CRT_SHADE_D
+#undef CRT_SHADE0
 #undef CRT_SHADE
       if (P.n_lights > 0 && P.strategy != CRT_STRATEGY_BSDF) {
 #define CRT_SHADOW(ST, W) \
@@ -1986,6 +2044,14 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
     ok = CRT_HIP_OK(hipMalloc(&r.d_materials, n_materials * sizeof(CrtMaterial))) &&
          CRT_HIP_OK(hipMemcpy(r.d_materials, materials, n_materials * sizeof(CrtMaterial), hipMemcpyHostToDevice));
   }
+  if (ok && n_materials) {  // the vertex code's per-material constants, derived on the device by the vertex code's own functions
+    ok = CRT_HIP_OK(hipMalloc(&r.d_mat_derived, n_materials * sizeof(DevMaterial)));
+    if (ok) {
+      hipLaunchKernelGGL(k_derive_materials, dim3((unsigned)((n_materials + 255) / 256)), dim3(256), 0, nullptr, r.d_materials,
+                         (uint32_t)n_materials, r.d_mat_derived);
+      ok = CRT_HIP_OK(hipGetLastError());
+    }
+  }
   if (ok && n_materials) {  // shade's partition key: one class byte per geom_id
     std::vector<uint8_t> cls(n_materials);
     bool seen[kClasses] = {false, false, false, false};
@@ -2022,7 +2088,7 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
     simple = simple && knobs.simple != 0;  // CRT_SIMPLE=0: the general instance (A/B, tests)
     r.mats_kind = r.has_media ? 2 : (simple ? 0 : 1);
   }
-  P.materials = r.d_materials; P.lights = r.d_lights; P.pixel_index = r.d_pixels;
+  P.materials = r.d_materials; P.mat_derived = r.d_mat_derived; P.lights = r.d_lights; P.pixel_index = r.d_pixels;
   P.mat_class = r.d_mat_class;
   P.media = r.d_media; P.media_by_id = r.d_media ? r.d_media + n_materials : nullptr;
   hipDeviceProp_t prop;
@@ -2046,6 +2112,7 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   r.cam_compact_ok = knobs.cam_compact != 0;
   r.noclassify_from = knobs.noclassify_from;
   r.shade_pipe = knobs.shade_pipe;
+  r.mat_derived = knobs.mat_derived != 0;
   r.tail_from = knobs.tail_from;
   r.max_batch_slots = knobs.max_batch_slots;
   r.n_lanes = knobs.lanes < 1 ? 1 : (knobs.lanes > Renderer::kMaxLanes ? Renderer::kMaxLanes : knobs.lanes);

@@ -60,10 +60,18 @@ __device__ __forceinline__ void roughness_to_alpha(float roughness, float anisot
   ax = rmax(x, 1e-4f);
   ay = rmax(y, 1e-4f);
 }
-__device__ __forceinline__ float ggx_d(float n_dot_h, float h_dot_t, float h_dot_b, float ax, float ay) {
-  const float tx = h_dot_t / ax, ty = h_dot_b / ay;
+// A lobe's GGX roughness pair with the product that opens ggx_d's denominator: all three follow from the material alone.
+struct Alpha { float ax, ay, pi_axay; };
+__device__ __forceinline__ Alpha alpha_of(float roughness, float anisotropy) {
+  Alpha a;
+  roughness_to_alpha(roughness, anisotropy, a.ax, a.ay);
+  a.pi_axay = CRT_PI * a.ax * a.ay;
+  return a;
+}
+__device__ __forceinline__ float ggx_d(float n_dot_h, float h_dot_t, float h_dot_b, const Alpha &a) {
+  const float tx = h_dot_t / a.ax, ty = h_dot_b / a.ay;
   const float term = tx * tx + ty * ty + n_dot_h * n_dot_h;
-  return 1.0f / (CRT_PI * ax * ay * term * term);
+  return 1.0f / (a.pi_axay * term * term);
 }
 __device__ __forceinline__ float ggx_lambda(float v_dot_n, float v_dot_t, float v_dot_b, float ax, float ay) {
   const float vt = v_dot_t * ax, vb = v_dot_b * ay;
@@ -92,19 +100,19 @@ __device__ __forceinline__ V3 sample_vndf(V3 v_local, float ax, float ay, float 
   const V3 nh = t1 * t1c + t2 * t2c + vh * sqrtf(rmax(1.0f - t1c * t1c - t2c * t2c, 0.0f));
   return normalize(v3(ax * nh.x, ay * nh.y, rmax(nh.z, 0.0f)));
 }
-__device__ __forceinline__ float pdf_vndf(V3 v_local, V3 h_local, float ax, float ay) {
+__device__ __forceinline__ float pdf_vndf(V3 v_local, V3 h_local, const Alpha &a) {
   const float n_dot_v = rmax(v_local.z, 1e-6f);
   const float n_dot_h = rmax(h_local.z, 1e-6f);
-  const float d = ggx_d(n_dot_h, h_local.x, h_local.y, ax, ay);
-  const float lambda_v = ggx_lambda(n_dot_v, v_local.x, v_local.y, ax, ay);
+  const float d = ggx_d(n_dot_h, h_local.x, h_local.y, a);
+  const float lambda_v = ggx_lambda(n_dot_v, v_local.x, v_local.y, a.ax, a.ay);
   const float g1 = 1.0f / (1.0f + lambda_v);
   return d * g1 / (4.0f * n_dot_v);
 }
-__device__ __forceinline__ float pdf_vndf_h(V3 v_local, V3 h_local, float ax, float ay) {
+__device__ __forceinline__ float pdf_vndf_h(V3 v_local, V3 h_local, const Alpha &a) {
   const float n_dot_v = rmax(v_local.z, 1e-6f);
   const float v_dot_h = rmax(dot(v_local, h_local), 0.0f);
-  const float d = ggx_d(rmax(h_local.z, 1e-6f), h_local.x, h_local.y, ax, ay);
-  const float lambda_v = ggx_lambda(n_dot_v, v_local.x, v_local.y, ax, ay);
+  const float d = ggx_d(rmax(h_local.z, 1e-6f), h_local.x, h_local.y, a);
+  const float lambda_v = ggx_lambda(n_dot_v, v_local.x, v_local.y, a.ax, a.ay);
   const float g1 = 1.0f / (1.0f + lambda_v);
   return d * g1 * v_dot_h / n_dot_v;
 }
@@ -112,34 +120,56 @@ __device__ __forceinline__ float pdf_vndf_h(V3 v_local, V3 h_local, float ax, fl
 #define CRT_EON_A (0.5f - 2.0f / (3.0f * CRT_PI))
 #define CRT_EON_B (2.0f / 3.0f - 28.0f / (15.0f * CRT_PI))
 
-__device__ __forceinline__ float eon_albedo_approx(float mu, float roughness) {
+// What of the EON diffuse model follows from the albedo and the roughness alone (every operand of eon_diffuse that
+// holds no angle), each a whole sub-expression of the formula as the reference writes it.
+struct EonConst {
+  float roughness;
+  float denom;        // 1 + A * roughness: the divisor of both albedo approximations
+  V3 f_ss;            // rho * (af / pi): the single-scattering lobe before its angular factor
+  V3 f_ms;            // rho_ms * (1 / pi): the multiple-scattering lobe before its angular factor
+  float one_m_avg_e;  // max(1 - avg_e, EPS)
+};
+#define CRT_EON_EPS 1.0e-7f
+__device__ __forceinline__ EonConst eon_const(V3 rho, float roughness) {
+  EonConst k;
+  rho = vclamp(rho, splat(0.0f), splat(1.0f));
+  k.roughness = roughness;
+  k.denom = 1.0f + CRT_EON_A * roughness;
+  const float af = 1.0f / k.denom;
+  k.f_ss = rho * (af / CRT_PI);
+  const float avg_e = af * (1.0f + CRT_EON_B * roughness);
+  const V3 rho_ms = (rho * rho) * avg_e / (splat(1.0f) - rho * (1.0f - avg_e));
+  k.f_ms = rho_ms * (1.0f / CRT_PI);
+  k.one_m_avg_e = rmax(1.0f - avg_e, CRT_EON_EPS);
+  return k;
+}
+__device__ __forceinline__ float eon_albedo_approx(float mu, const EonConst &k) {
   const float mucomp = 1.0f - rclamp(mu, 0.0f, 1.0f);
   const float G1 = 0.057108529f, G2 = 0.49188187f, G3 = -0.33218144f, G4 = 0.071442995f;
   const float g_over_pi = mucomp * (G1 + mucomp * (G2 + mucomp * (G3 + mucomp * G4)));
-  return (1.0f + roughness * g_over_pi) / (1.0f + CRT_EON_A * roughness);
+  return (1.0f + k.roughness * g_over_pi) / k.denom;
 }
-__device__ __forceinline__ V3 eon_diffuse(V3 rho, float roughness, V3 v_local, V3 l_local) {
-  rho = vclamp(rho, splat(0.0f), splat(1.0f));
+__device__ __forceinline__ V3 eon_diffuse(const EonConst &k, V3 v_local, V3 l_local) {
   const float mu_i = v_local.z, mu_o = l_local.z;
   const float s = dot(v_local, l_local) - mu_i * mu_o;
   const float s_over_t = s > 0.0f ? s / rmax(rmax(mu_i, mu_o), 1e-6f) : s;
-  const float af = 1.0f / (1.0f + CRT_EON_A * roughness);
-  const V3 f_ss = rho * (af / CRT_PI) * (1.0f + roughness * s_over_t);
-  const float e_o = eon_albedo_approx(mu_o, roughness);
-  const float e_i = eon_albedo_approx(mu_i, roughness);
-  const float avg_e = af * (1.0f + CRT_EON_B * roughness);
-  const V3 rho_ms = (rho * rho) * avg_e / (splat(1.0f) - rho * (1.0f - avg_e));
-  const float EPS = 1.0e-7f;
-  const V3 f_ms = rho_ms * (1.0f / CRT_PI) * (rmax(1.0f - e_o, EPS) * rmax(1.0f - e_i, EPS) / rmax(1.0f - avg_e, EPS));
+  const V3 f_ss = k.f_ss * (1.0f + k.roughness * s_over_t);
+  const float e_o = eon_albedo_approx(mu_o, k);
+  const float e_i = eon_albedo_approx(mu_i, k);
+  const V3 f_ms = k.f_ms * (rmax(1.0f - e_o, CRT_EON_EPS) * rmax(1.0f - e_i, CRT_EON_EPS) / k.one_m_avg_e);
   return f_ss + f_ms;
 }
-__device__ __forceinline__ V3 fresnel_f82_tint(float cos_theta, V3 f0, V3 tint) {
+// The F82-tint Fresnel in two steps: the coefficient `a`, which the metal's F0 and tint fix, and the angular part.
+__device__ __forceinline__ V3 f82_tint_a(V3 f0, V3 tint) {
   const float MU_BAR = 1.0f / 7.0f;
-  const float mu = rclamp(cos_theta, 0.0f, 1.0f);
   const V3 one = splat(1.0f);
   const V3 fs_bar = f0 + (one - f0) * pow5_(1.0f - MU_BAR);
   const float denom = MU_BAR * pow6_(1.0f - MU_BAR);
-  const V3 a = fs_bar * (one - tint) / denom;
+  return fs_bar * (one - tint) / denom;
+}
+__device__ __forceinline__ V3 fresnel_f82_tint(float cos_theta, V3 f0, V3 a) {
+  const float mu = rclamp(cos_theta, 0.0f, 1.0f);
+  const V3 one = splat(1.0f);
   const V3 fs_mu = f0 + (one - f0) * pow5_(1.0f - mu);
   return vclamp(fs_mu - a * mu * pow6_(1.0f - mu), splat(0.0f), one);
 }
@@ -257,33 +287,134 @@ __device__ __forceinline__ int lobe_pick(const LobePmf &p, float u) {  // openpb
   return LOBE_TRANSMISSION;
 }
 
-__device__ __forceinline__ V3 eval_diffuse(const CrtMaterial &m, V3 v_local, V3 l_local, float f_avg_diel) {
+// ---- material views ----
+// The reference works every per-material constant out again at each call (openpbr.rs "recomputed per call"). The vertex
+// code below is written ONCE, over a view of the material that answers for those constants:
+//   MatRaw      computes each one on the spot from the CrtMaterial record, as the reference does — what the seam entry
+//               points (shade_seam.hip), the general kernel instances and CRT_MAT_DERIVED=0 run;
+//   MatDerived  reads it from a DevMaterial record that derive_material() filled once per renderer THROUGH MatRaw, so no
+//               formula exists twice and every stored value has the bits the vertex would have computed
+//               (-ffp-contract=off: one IEEE operation gives one result wherever it runs).
+// Only whole material-only sub-expressions are stored; `x / d` with a per-vertex x stays a division by the stored d.
+// DevMaterial covers what a hit on a SIMPLE table reads; the arms SIMPLE compiles out (coat, fuzz, thin film, rough
+// transmission) and the thin pass-through arm keep reading the raw record through raw(). The record has the size of a
+// CrtMaterial so that every LDS budget of the shade kernels (pathtrace.hip) holds for either table.
+struct DevMaterial {
+  uint32_t kind;
+  float emission[3];         // Emissive: the radiance; OpenPBR: emission_color * emission_luminance
+  float pmf[5];              // lobe_pmf
+  float spec_alpha[3];       // alpha_of(specular roughness, anisotropy): ax, ay, pi * ax * ay
+  float coat_alpha[3];       // ... of the coat (pdf_all weighs the coat lobe in every material: p_coat is floored)
+  float f0_diel, one_m_f0_diel;
+  float presence;            // of the diffuse base
+  float eon_roughness, eon_denom, eon_f_ss[3], eon_f_ms[3], eon_one_m_avg_e;  // EonConst
+  float metalness, one_m_metalness, specular_weight;
+  float f0_diel_base[3], metal_f0[3], f82_a[3];
+  float base_atten;
+  float pad[16];
+};
+static_assert(sizeof(DevMaterial) == sizeof(CrtMaterial), "either table is staged under the same LDS budget");
+
+struct MatRaw {
+  const CrtMaterial &m;
+  __device__ __forceinline__ const CrtMaterial &raw() const { return m; }
+  __device__ __forceinline__ uint32_t kind() const { return m.kind; }
+  __device__ __forceinline__ V3 emission() const {
+    return m.kind == CRT_MAT_EMISSIVE ? ld3(m.emission_color) : ld3(m.emission_color) * m.emission_luminance;
+  }
+  __device__ __forceinline__ LobePmf pmf() const { return lobe_pmf(m); }
+  __device__ __forceinline__ Alpha spec_alpha() const { return alpha_of(m.specular_roughness, m.specular_roughness_anisotropy); }
+  __device__ __forceinline__ Alpha coat_alpha() const { return alpha_of(m.coat_roughness, m.coat_roughness_anisotropy); }
+  __device__ __forceinline__ float f0_diel() const { return f0_from_ior(m.specular_ior); }
+  __device__ __forceinline__ float one_m_f0_diel() const { return 1.0f - f0_diel(); }
+  __device__ __forceinline__ float presence() const {
+    return m.base_weight * (1.0f - m.base_metalness) * (1.0f - m.transmission_weight);
+  }
+  __device__ __forceinline__ EonConst eon() const {
+    const V3 diffuse_color = lerp(ld3(m.base_color), ld3(m.subsurface_color), m.subsurface_weight);
+    const V3 rho = diffuse_color * presence();
+    return eon_const(rho, m.base_diffuse_roughness);
+  }
+  __device__ __forceinline__ float metalness() const { return m.base_metalness; }
+  __device__ __forceinline__ float one_m_metalness() const { return 1.0f - m.base_metalness; }
+  __device__ __forceinline__ float specular_weight() const { return m.specular_weight; }
+  __device__ __forceinline__ V3 f0_diel_base() const { return ld3(m.specular_color) * f0_diel() * m.specular_weight; }
+  __device__ __forceinline__ V3 metal_f0() const { return ld3(m.base_color) * m.base_weight; }
+  __device__ __forceinline__ V3 f82_a() const { return f82_tint_a(metal_f0(), ld3(m.specular_color)); }
+  __device__ __forceinline__ float base_atten() const { return rclamp(1.0f - m.fuzz_weight, 0.0f, 1.0f); }
+};
+struct MatDerived {
+  const DevMaterial &d;
+  const CrtMaterial &r;  // the record d was derived from: only the arms named above read it
+  __device__ __forceinline__ const CrtMaterial &raw() const { return r; }
+  __device__ __forceinline__ uint32_t kind() const { return d.kind; }
+  __device__ __forceinline__ V3 emission() const { return ld3(d.emission); }
+  __device__ __forceinline__ LobePmf pmf() const { return LobePmf{d.pmf[0], d.pmf[1], d.pmf[2], d.pmf[3], d.pmf[4]}; }
+  __device__ __forceinline__ Alpha spec_alpha() const { return Alpha{d.spec_alpha[0], d.spec_alpha[1], d.spec_alpha[2]}; }
+  __device__ __forceinline__ Alpha coat_alpha() const { return Alpha{d.coat_alpha[0], d.coat_alpha[1], d.coat_alpha[2]}; }
+  __device__ __forceinline__ float f0_diel() const { return d.f0_diel; }
+  __device__ __forceinline__ float one_m_f0_diel() const { return d.one_m_f0_diel; }
+  __device__ __forceinline__ float presence() const { return d.presence; }
+  __device__ __forceinline__ EonConst eon() const {
+    return EonConst{d.eon_roughness, d.eon_denom, ld3(d.eon_f_ss), ld3(d.eon_f_ms), d.eon_one_m_avg_e};
+  }
+  __device__ __forceinline__ float metalness() const { return d.metalness; }
+  __device__ __forceinline__ float one_m_metalness() const { return d.one_m_metalness; }
+  __device__ __forceinline__ float specular_weight() const { return d.specular_weight; }
+  __device__ __forceinline__ V3 f0_diel_base() const { return ld3(d.f0_diel_base); }
+  __device__ __forceinline__ V3 metal_f0() const { return ld3(d.metal_f0); }
+  __device__ __forceinline__ V3 f82_a() const { return ld3(d.f82_a); }
+  __device__ __forceinline__ float base_atten() const { return d.base_atten; }
+};
+__device__ __forceinline__ void st3(float c[3], V3 a) { c[0] = a.x; c[1] = a.y; c[2] = a.z; }
+// One DevMaterial from one CrtMaterial: every field is what MatRaw answers. (Of an Emissive record only kind and
+// emission are ever read back; the rest is arithmetic on fields the record does not define, and is never looked at.)
+__device__ __forceinline__ void derive_material(const CrtMaterial &m, DevMaterial &o) {
+  const MatRaw v{m};
+  o.kind = v.kind();
+  st3(o.emission, v.emission());
+  const LobePmf p = v.pmf();
+  o.pmf[0] = p.p_diffuse; o.pmf[1] = p.p_specular; o.pmf[2] = p.p_coat; o.pmf[3] = p.p_fuzz; o.pmf[4] = p.p_transmission;
+  const Alpha a = v.spec_alpha(), ac = v.coat_alpha();
+  o.spec_alpha[0] = a.ax; o.spec_alpha[1] = a.ay; o.spec_alpha[2] = a.pi_axay;
+  o.coat_alpha[0] = ac.ax; o.coat_alpha[1] = ac.ay; o.coat_alpha[2] = ac.pi_axay;
+  o.f0_diel = v.f0_diel(); o.one_m_f0_diel = v.one_m_f0_diel();
+  o.presence = v.presence();
+  const EonConst k = v.eon();
+  o.eon_roughness = k.roughness; o.eon_denom = k.denom; st3(o.eon_f_ss, k.f_ss); st3(o.eon_f_ms, k.f_ms);
+  o.eon_one_m_avg_e = k.one_m_avg_e;
+  o.metalness = v.metalness(); o.one_m_metalness = v.one_m_metalness(); o.specular_weight = v.specular_weight();
+  st3(o.f0_diel_base, v.f0_diel_base()); st3(o.metal_f0, v.metal_f0()); st3(o.f82_a, v.f82_a());
+  o.base_atten = v.base_atten();
+  for (int i = 0; i < 16; i++) o.pad[i] = 0.0f;
+}
+
+template <class MV>
+__device__ __forceinline__ V3 eval_diffuse(const MV &mv, V3 v_local, V3 l_local) {
   if (l_local.z <= 0.0f || v_local.z <= 0.0f) return splat(0.0f);
-  const float presence = m.base_weight * (1.0f - m.base_metalness) * (1.0f - m.transmission_weight);
-  if (presence <= 0.0f) return splat(0.0f);
-  const V3 diffuse_color = lerp(ld3(m.base_color), ld3(m.subsurface_color), m.subsurface_weight);
-  const V3 rho = diffuse_color * presence;
-  return eon_diffuse(rho, m.base_diffuse_roughness, v_local, l_local) * (1.0f - f_avg_diel);
+  if (mv.presence() <= 0.0f) return splat(0.0f);
+  return eon_diffuse(mv.eon(), v_local, l_local) * mv.one_m_f0_diel();
 }
 
 // SIMPLE (here and below): no material of the scene has a coat, fuzz, thin film, transmission or subsurface
 // (material class <= 1 for the whole table, pathtrace.hip). The arms those weights gate are then compiled out — they are
 // never taken, so nothing changes but the kernel: the thin-film Airy sums, the coat passage's pow(), the sheen, rough
 // transmission with dispersion are the largest bodies and the heaviest users of f64 constants in the vertex code.
-template <bool SIMPLE>
-__device__ __forceinline__ V3 eval_specular(const CrtMaterial &m, V3 v_local, V3 l_local, V3 h_local, float ax, float ay) {
+template <bool SIMPLE, class MV>
+__device__ __forceinline__ V3 eval_specular(const MV &mv, V3 v_local, V3 l_local, V3 h_local, const Alpha &a) {
+  const CrtMaterial &m = mv.raw();  // the thin-film and thin-wall arms
   const float n_dot_v = rmax(v_local.z, 1e-4f);
   const float n_dot_l = rmax(l_local.z, 1e-4f);
   const float n_dot_h = rmax(h_local.z, 1e-4f);
   const float v_dot_h = rmax(dot(v_local, h_local), 1e-4f);
-  const float d = ggx_d(n_dot_h, h_local.x, h_local.y, ax, ay);
-  const float g = ggx_g2(n_dot_v, v_local.x, v_local.y, n_dot_l, l_local.x, l_local.y, ax, ay);
-  const float f0_diel_scalar = f0_from_ior(m.specular_ior);
+  const float d = ggx_d(n_dot_h, h_local.x, h_local.y, a);
+  const float g = ggx_g2(n_dot_v, v_local.x, v_local.y, n_dot_l, l_local.x, l_local.y, a.ax, a.ay);
+  const float metalness = mv.metalness();
   const float outer_ior = m.coat_weight > 0.0f ? m.coat_ior : 1.0f;
   const float tf_thickness_nm = m.thin_film_thickness * 1000.0f;
   V3 diel_term = splat(0.0f);
-  if (m.base_metalness < 1.0f) {
-    const V3 f0_diel_base = ld3(m.specular_color) * f0_diel_scalar * m.specular_weight;
+  if (metalness < 1.0f) {
+    const V3 f0_diel_base = mv.f0_diel_base();
     V3 f_diel;
     if (!SIMPLE && m.thin_film_weight > 0.0f) {
       const V3 f_normal = fresnel_schlick(v_dot_h, f0_diel_base);
@@ -293,16 +424,16 @@ __device__ __forceinline__ V3 eval_specular(const CrtMaterial &m, V3 v_local, V3
       f_diel = fresnel_schlick(v_dot_h, f0_diel_base);
     }
     if (!SIMPLE && m.thin_walled && m.transmission_weight > 0.0f) {
-      const float f_phys = fresnel_schlick_scalar(v_dot_h, f0_diel_scalar);
+      const float f_phys = fresnel_schlick_scalar(v_dot_h, mv.f0_diel());
       const float boost = 2.0f / (1.0f + f_phys);
       f_diel = f_diel * (1.0f + (boost - 1.0f) * m.transmission_weight);
     }
-    diel_term = f_diel * (1.0f - m.base_metalness);
+    diel_term = f_diel * mv.one_m_metalness();
   }
   V3 metal_term = splat(0.0f);
-  if (m.base_metalness > 0.0f) {
-    const V3 metal_f0 = ld3(m.base_color) * m.base_weight;
-    const V3 f_metal_base = fresnel_f82_tint(v_dot_h, metal_f0, ld3(m.specular_color));
+  if (metalness > 0.0f) {
+    const V3 metal_f0 = mv.metal_f0();
+    const V3 f_metal_base = fresnel_f82_tint(v_dot_h, metal_f0, mv.f82_a());
     V3 f_metal;
     if (!SIMPLE && m.thin_film_weight > 0.0f) {
       const V3 f_iri = thin_film_fresnel_metal(v_dot_h, outer_ior, m.thin_film_ior, metal_f0, tf_thickness_nm);
@@ -310,20 +441,20 @@ __device__ __forceinline__ V3 eval_specular(const CrtMaterial &m, V3 v_local, V3
     } else {
       f_metal = f_metal_base;
     }
-    f_metal = f_metal * m.specular_weight;
-    metal_term = f_metal * m.base_metalness;
+    f_metal = f_metal * mv.specular_weight();
+    metal_term = f_metal * metalness;
   }
   const float brdf = d * g / (4.0f * n_dot_v * n_dot_l);
   return (metal_term + diel_term) * brdf;
 }
 
-__device__ __forceinline__ V3 eval_coat(const CrtMaterial &m, V3 v_local, V3 l_local, V3 h_local, float ax, float ay) {
+__device__ __forceinline__ V3 eval_coat(const CrtMaterial &m, V3 v_local, V3 l_local, V3 h_local, const Alpha &a) {
   const float n_dot_v = rmax(v_local.z, 1e-4f);
   const float n_dot_l = rmax(l_local.z, 1e-4f);
   const float n_dot_h = rmax(h_local.z, 1e-4f);
   const float v_dot_h = rmax(dot(v_local, h_local), 1e-4f);
-  const float d = ggx_d(n_dot_h, h_local.x, h_local.y, ax, ay);
-  const float g = ggx_g2(n_dot_v, v_local.x, v_local.y, n_dot_l, l_local.x, l_local.y, ax, ay);
+  const float d = ggx_d(n_dot_h, h_local.x, h_local.y, a);
+  const float g = ggx_g2(n_dot_v, v_local.x, v_local.y, n_dot_l, l_local.x, l_local.y, a.ax, a.ay);
   const float f = fresnel_schlick_scalar(v_dot_h, f0_from_ior(m.coat_ior));
   const float brdf = d * g / (4.0f * n_dot_v * n_dot_l);
   return splat(m.coat_weight * f * brdf);
@@ -373,8 +504,8 @@ __device__ __forceinline__ V3 dispersive_ior(float n_d, float abbe, float scale)
 __device__ __forceinline__ V3 transmission_iors(const CrtMaterial &m) {
   return dispersive_ior(m.specular_ior, m.transmission_dispersion_abbe_number, m.transmission_dispersion_scale);
 }
-__device__ __forceinline__ void transmission_alphas(const CrtMaterial &m, float &ax, float &ay) {
-  roughness_to_alpha(rmax(m.specular_roughness, 0.01f), m.specular_roughness_anisotropy, ax, ay);
+__device__ __forceinline__ Alpha transmission_alphas(const CrtMaterial &m) {
+  return alpha_of(rmax(m.specular_roughness, 0.01f), m.specular_roughness_anisotropy);
 }
 __device__ __forceinline__ void eval_transmission_channel(const CrtMaterial &m, V3 v_local, V3 l_local, bool entering,
                                                           float ior, float &btdf_o, float &pdf_o) {  // Walter 2007
@@ -387,18 +518,17 @@ __device__ __forceinline__ void eval_transmission_channel(const CrtMaterial &m, 
   const float v_dot_h = dot(v_local, h);
   const float l_dot_h = dot(l_local, h);
   if (v_dot_h <= 1e-6f || l_dot_h >= -1e-6f) return;
-  float ax, ay;
-  transmission_alphas(m, ax, ay);
+  const Alpha a = transmission_alphas(m);
   const float n_dot_v = rmax(v_local.z, 1e-6f);
   const float n_dot_l = rmax(-l_local.z, 1e-6f);
-  const float d = ggx_d(rmax(h.z, 1e-6f), h.x, h.y, ax, ay);
-  const float g = ggx_g2(n_dot_v, v_local.x, v_local.y, n_dot_l, l_local.x, l_local.y, ax, ay);
+  const float d = ggx_d(rmax(h.z, 1e-6f), h.x, h.y, a);
+  const float g = ggx_g2(n_dot_v, v_local.x, v_local.y, n_dot_l, l_local.x, l_local.y, a.ax, a.ay);
   const float f = fresnel_dielectric(v_dot_h, eta_i, eta_t);
   const float denom = eta_i * v_dot_h + eta_t * l_dot_h;
   const float denom2 = denom * denom;
   if (denom2 < 1e-10f) return;
   const float btdf = (v_dot_h * -l_dot_h) / (n_dot_v * n_dot_l) * (eta_t * eta_t * (1.0f - f) * d * g / denom2);
-  const float p_h = pdf_vndf_h(v_local, h, ax, ay);
+  const float p_h = pdf_vndf_h(v_local, h, a);
   const float jacobian = eta_t * eta_t * -l_dot_h / denom2;
   btdf_o = rmax(btdf, 0.0f);
   pdf_o = p_h * jacobian;
@@ -427,8 +557,9 @@ __device__ __forceinline__ void eval_transmission(const CrtMaterial &m, V3 v_loc
   pdf = acc;
 }
 
-template <bool SIMPLE>
-__device__ __forceinline__ V3 eval_all(const CrtMaterial &m, V3 v_local, V3 l_local, bool entering) {  // :629-683
+template <bool SIMPLE, class MV>
+__device__ __forceinline__ V3 eval_all(const MV &mv, V3 v_local, V3 l_local, bool entering) {  // :629-683
+  const CrtMaterial &m = mv.raw();  // the arms SIMPLE compiles out
   if (v_local.z <= 0.0f) return splat(0.0f);
   if (l_local.z <= 0.0f) {
     if (SIMPLE || !transmission_is_continuous(m)) return splat(0.0f);
@@ -437,25 +568,18 @@ __device__ __forceinline__ V3 eval_all(const CrtMaterial &m, V3 v_local, V3 l_lo
     return val;
   }
   const V3 h_local = normalize(v_local + l_local);
-  float ax, ay;
-  roughness_to_alpha(m.specular_roughness, m.specular_roughness_anisotropy, ax, ay);
-  const float f_avg_diel = f0_from_ior(m.specular_ior);
-  const V3 diffuse = eval_diffuse(m, v_local, l_local, f_avg_diel);
-  const V3 specular = eval_specular<SIMPLE>(m, v_local, l_local, h_local, ax, ay);
+  const V3 diffuse = eval_diffuse(mv, v_local, l_local);
+  const V3 specular = eval_specular<SIMPLE>(mv, v_local, l_local, h_local, mv.spec_alpha());
   V3 coat = splat(0.0f);
-  if (!SIMPLE && m.coat_weight > 0.0f) {
-    float axc, ayc;
-    roughness_to_alpha(m.coat_roughness, m.coat_roughness_anisotropy, axc, ayc);
-    coat = eval_coat(m, v_local, l_local, h_local, axc, ayc);
-  }
+  if (!SIMPLE && m.coat_weight > 0.0f) coat = eval_coat(m, v_local, l_local, h_local, mv.coat_alpha());
   const V3 fuzz = (!SIMPLE && m.fuzz_weight > 0.0f) ? eval_fuzz(m, v_local, l_local, h_local) : splat(0.0f);
   const V3 coat_atten = coat_attenuation<SIMPLE>(m, v_local.z, l_local.z);
-  const float base_atten = rclamp(1.0f - m.fuzz_weight, 0.0f, 1.0f);
-  return fuzz + (coat + coat_atten * (diffuse + specular)) * base_atten;
+  return fuzz + (coat + coat_atten * (diffuse + specular)) * mv.base_atten();
 }
 
-template <bool SIMPLE>
-__device__ __forceinline__ float pdf_all(const CrtMaterial &m, const LobePmf &pmf, V3 v_local, V3 l_local, bool entering) {
+template <bool SIMPLE, class MV>
+__device__ __forceinline__ float pdf_all(const MV &mv, const LobePmf &pmf, V3 v_local, V3 l_local, bool entering) {
+  const CrtMaterial &m = mv.raw();  // the transmission arm
   if (v_local.z <= 0.0f) return 0.0f;  // openpbr.rs:689-722
   if (l_local.z <= 0.0f) {
     if (SIMPLE || !transmission_is_continuous(m)) return 0.0f;
@@ -464,12 +588,9 @@ __device__ __forceinline__ float pdf_all(const CrtMaterial &m, const LobePmf &pm
     return pmf.p_transmission * p;
   }
   const V3 h_local = normalize(v_local + l_local);
-  float ax, ay, axc, ayc;
-  roughness_to_alpha(m.specular_roughness, m.specular_roughness_anisotropy, ax, ay);
-  roughness_to_alpha(m.coat_roughness, m.coat_roughness_anisotropy, axc, ayc);
   const float pdf_cosine = rmax(l_local.z, 0.0f) / CRT_PI;
-  const float pdf_specular = pdf_vndf(v_local, h_local, ax, ay);
-  const float pdf_coat = pdf_vndf(v_local, h_local, axc, ayc);
+  const float pdf_specular = pdf_vndf(v_local, h_local, mv.spec_alpha());
+  const float pdf_coat = pdf_vndf(v_local, h_local, mv.coat_alpha());
   return pmf.p_diffuse * pdf_cosine + pmf.p_specular * pdf_specular + pmf.p_coat * pdf_coat + pmf.p_fuzz * pdf_cosine;
 }
 
@@ -484,9 +605,8 @@ __device__ __forceinline__ bool sample_transmission_rough(const CrtMaterial &m, 
   } else ior = iors.y;
   const float eta_i = entering ? 1.0f : ior, eta_t = entering ? ior : 1.0f;
   const float eta_rel = eta_i / eta_t;
-  float ax, ay;
-  transmission_alphas(m, ax, ay);
-  const V3 h = sample_vndf(v_local, ax, ay, u1, u2);
+  const Alpha a = transmission_alphas(m);
+  const V3 h = sample_vndf(v_local, a.ax, a.ay, u1, u2);
   const float cos_i = dot(v_local, h);
   if (cos_i <= 1e-6f) return false;
   const float sin2_t = eta_rel * eta_rel * (1.0f - cos_i * cos_i);
@@ -521,10 +641,11 @@ __device__ __forceinline__ V3 to_world(const Frame3 &f, V3 l) { return f.t * l.x
 
 // Material::scatter_importance (material.rs:40-45): OpenPBR::scatter_resolved (openpbr.rs:1026-1136);
 // Emissive never scatters (emissive.rs:30-38).
-template <bool SIMPLE>
-__device__ bool mat_scatter(const CrtMaterial &m, V3 ray_dir, const HitRec &rec, Sampler dom, Scatter &out,
+template <bool SIMPLE, class MV>
+__device__ bool mat_scatter(const MV &mv, V3 ray_dir, const HitRec &rec, Sampler dom, Scatter &out,
                             const uint32_t *sobol_tab) {
-  if (m.kind == CRT_MAT_EMISSIVE) return false;
+  const CrtMaterial &m = mv.raw();  // the transmission arms
+  if (mv.kind() == CRT_MAT_EMISSIVE) return false;
   out.medium = false;
   const Frame3 frame = frame_new(rec.normal);
   const V3 v_world = -normalize(ray_dir);
@@ -532,7 +653,7 @@ __device__ bool mat_scatter(const CrtMaterial &m, V3 ray_dir, const HitRec &rec,
   if (v_local.z <= 0.0f) return false;
   float s[4];
   draw_sample4(dom, s, sobol_tab);
-  const LobePmf pmf = lobe_pmf(m);
+  const LobePmf pmf = mv.pmf();
   const int lobe = lobe_pick(pmf, s[0]);
   if (lobe == LOBE_TRANSMISSION) {
     // SIMPLE keeps this arm's thin form: lobe_pick falls through to LOBE_TRANSMISSION whenever u lands past the
@@ -541,8 +662,8 @@ __device__ bool mat_scatter(const CrtMaterial &m, V3 ray_dir, const HitRec &rec,
       V3 l_local;
       if (!sample_transmission_rough(m, v_local, rec.front_face, s[3], s[1], s[2], l_local)) return false;
       const V3 l_world = to_world(frame, l_local);
-      const float pdf = rmax(pdf_all<SIMPLE>(m, pmf, v_local, l_local, rec.front_face), 1e-4f);
-      const V3 brdf = eval_all<SIMPLE>(m, v_local, l_local, rec.front_face);
+      const float pdf = rmax(pdf_all<SIMPLE>(mv, pmf, v_local, l_local, rec.front_face), 1e-4f);
+      const V3 brdf = eval_all<SIMPLE>(mv, v_local, l_local, rec.front_face);
       out.origin = rec.p + l_world * 1e-4f;
       out.dir = l_world;
       out.value = brdf * fabs_(l_local.z);
@@ -561,16 +682,14 @@ __device__ bool mat_scatter(const CrtMaterial &m, V3 ray_dir, const HitRec &rec,
   if (lobe == LOBE_DIFFUSE || lobe == LOBE_FUZZ) {
     l_local = cosine_hemisphere(s[1], s[2]);
   } else {
-    float ax, ay;
-    if (lobe == LOBE_SPECULAR) roughness_to_alpha(m.specular_roughness, m.specular_roughness_anisotropy, ax, ay);
-    else roughness_to_alpha(m.coat_roughness, m.coat_roughness_anisotropy, ax, ay);
-    const V3 h_local = sample_vndf(v_local, ax, ay, s[1], s[2]);
+    const Alpha a = lobe == LOBE_SPECULAR ? mv.spec_alpha() : mv.coat_alpha();
+    const V3 h_local = sample_vndf(v_local, a.ax, a.ay, s[1], s[2]);
     const V3 l = h_local * (2.0f * dot(v_local, h_local)) - v_local;
     if (l.z <= 0.0f) return false;
     l_local = l;
   }
-  const float pdf = rmax(pdf_all<SIMPLE>(m, pmf, v_local, l_local, rec.front_face), 1e-4f);
-  const V3 brdf = eval_all<SIMPLE>(m, v_local, l_local, rec.front_face);
+  const float pdf = rmax(pdf_all<SIMPLE>(mv, pmf, v_local, l_local, rec.front_face), 1e-4f);
+  const V3 brdf = eval_all<SIMPLE>(mv, v_local, l_local, rec.front_face);
   const float n_dot_l = rmax(l_local.z, 0.0f);
   out.origin = rec.p;
   out.dir = to_world(frame, l_local);
@@ -581,27 +700,43 @@ __device__ bool mat_scatter(const CrtMaterial &m, V3 ray_dir, const HitRec &rec,
 }
 
 // Material::eval (material.rs:71-74): OpenPBR::eval_resolved (openpbr.rs:1138-1158); None for Emissive.
-template <bool SIMPLE>
-__device__ bool mat_eval(const CrtMaterial &m, V3 ray_dir, const HitRec &rec, V3 wi, V3 &value, float &pdf) {
-  if (m.kind == CRT_MAT_EMISSIVE) return false;
+template <bool SIMPLE, class MV>
+__device__ bool mat_eval(const MV &mv, V3 ray_dir, const HitRec &rec, V3 wi, V3 &value, float &pdf) {
+  if (mv.kind() == CRT_MAT_EMISSIVE) return false;
   const Frame3 frame = frame_new(rec.normal);
   const V3 v_local = to_local(frame, -normalize(ray_dir));
   if (v_local.z <= 0.0f) return false;
   const V3 l_local = to_local(frame, normalize(wi));
-  const LobePmf pmf = lobe_pmf(m);
-  pdf = rmax(pdf_all<SIMPLE>(m, pmf, v_local, l_local, rec.front_face), 1e-4f);
-  value = eval_all<SIMPLE>(m, v_local, l_local, rec.front_face) * fabs_(l_local.z);
+  const LobePmf pmf = mv.pmf();
+  pdf = rmax(pdf_all<SIMPLE>(mv, pmf, v_local, l_local, rec.front_face), 1e-4f);
+  value = eval_all<SIMPLE>(mv, v_local, l_local, rec.front_face) * fabs_(l_local.z);
   return true;
 }
 
 // Material::emitted_directional (material.rs:112-115; openpbr.rs:1211-1218).
-template <bool SIMPLE>
-__device__ __forceinline__ V3 mat_emitted_directional(const CrtMaterial &m, float cos_theta_o) {
-  if (m.kind == CRT_MAT_EMISSIVE) return ld3(m.emission_color);
-  const V3 uncoated = ld3(m.emission_color) * m.emission_luminance;
-  if (SIMPLE || m.coat_weight <= 0.0f) return uncoated;
+template <bool SIMPLE, class MV>
+__device__ __forceinline__ V3 mat_emitted_directional(const MV &mv, float cos_theta_o) {
+  const V3 uncoated = mv.emission();  // an Emissive's radiance as it stands
+  if (SIMPLE || mv.kind() == CRT_MAT_EMISSIVE) return uncoated;
+  const CrtMaterial &m = mv.raw();
+  if (m.coat_weight <= 0.0f) return uncoated;
   const V3 dark = coat_darkening_factor(ld3(m.base_color), m.coat_ior, m.coat_darkening);
   return uncoated * coat_passage(m, cos_theta_o) * dark;
+}
+
+// The three methods on a CrtMaterial record as it stands (the seam entry points, the general kernel instances).
+template <bool SIMPLE>
+__device__ __forceinline__ bool mat_scatter(const CrtMaterial &m, V3 ray_dir, const HitRec &rec, Sampler dom, Scatter &out,
+                                            const uint32_t *sobol_tab) {
+  return mat_scatter<SIMPLE, MatRaw>(MatRaw{m}, ray_dir, rec, dom, out, sobol_tab);
+}
+template <bool SIMPLE>
+__device__ __forceinline__ bool mat_eval(const CrtMaterial &m, V3 ray_dir, const HitRec &rec, V3 wi, V3 &value, float &pdf) {
+  return mat_eval<SIMPLE, MatRaw>(MatRaw{m}, ray_dir, rec, wi, value, pdf);
+}
+template <bool SIMPLE>
+__device__ __forceinline__ V3 mat_emitted_directional(const CrtMaterial &m, float cos_theta_o) {
+  return mat_emitted_directional<SIMPLE, MatRaw>(MatRaw{m}, cos_theta_o);
 }
 
 // ---- light.rs: area lights ----

@@ -3,13 +3,14 @@
     python profiles/isa_resources.py > profiles/r02_isa_resources.txt
 Compiles kernels/pathtrace.hip and kernels/traverse.hip to assembly with the Makefile's flags and reads the
 `amdhsa.kernels` metadata (VGPRs, spilled VGPRs, SGPRs spilled to VGPR lanes, scratch and LDS bytes) and counts the
-instruction classes of each kernel's body."""
+instruction classes of each kernel's body; `div` and `sqrt` are the IEEE f32 divisions (one v_div_fixup_f32 each) and
+square roots (v_sqrt_f32) the body holds."""
 import collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "crust-render_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I../../include",
          "-fno-slp-vectorize", "-O2", "-mllvm", "-amdgpu-set-wave-priority", "--cuda-device-only", "-S"]
-print("%-64s %5s %6s %6s %7s %6s | %6s %6s %6s %7s %5s %5s %7s" % ("kernel", "vgpr", "vspill", "sspill", "scratch", "lds", "instr", "valu", "v_mov", "cndmask", "vmem", "lds", "lane_rw"))
+print("%-64s %5s %6s %6s %7s %6s | %6s %6s %6s %7s %5s %5s %7s %5s %5s" % ("kernel", "vgpr", "vspill", "sspill", "scratch", "lds", "instr", "valu", "v_mov", "cndmask", "vmem", "lds", "lane_rw", "div", "sqrt"))
 for src in ("kernels/pathtrace.hip", "kernels/traverse.hip"):
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + [src, "-o", tmp.name], cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
@@ -33,6 +34,8 @@ for src in ("kernels/pathtrace.hip", "kernels/traverse.hip"):
                 c["v_mov"] += op.startswith("v_mov")
                 c["cndmask"] += op.startswith("v_cndmask")
                 c["lane_rw"] += op.startswith(("v_readlane", "v_writelane"))
+                c["div"] += op.startswith("v_div_fixup_f32")
+                c["sqrt"] += op.startswith("v_sqrt_f32")
             elif op.startswith(("global_", "flat_", "scratch_", "buffer_")):
                 c["vmem"] += 1
             elif op.startswith("ds_"):
@@ -41,4 +44,4 @@ for src in ("kernels/pathtrace.hip", "kernels/traverse.hip"):
         dem = re.sub(r"\(anonymous namespace\)::", "", dem)
         dem = re.sub(r"\(.*", "", dem).replace("void crt::", "")
         m = meta[name]
-        print("%-64s %5s %6s %6s %7s %6s | %6d %6d %6d %7d %5d %5d %7d" % (dem[:64], m[0], m[1], m[2], m[3], m[4], c["instr"], c["valu"], c["v_mov"], c["cndmask"], c["vmem"], c["lds"], c["lane_rw"]))
+        print("%-64s %5s %6s %6s %7s %6s | %6d %6d %6d %7d %5d %5d %7d %5d %5d" % (dem[:64], m[0], m[1], m[2], m[3], m[4], c["instr"], c["valu"], c["v_mov"], c["cndmask"], c["vmem"], c["lds"], c["lane_rw"], c["div"], c["sqrt"]))
