@@ -8,6 +8,9 @@
 // The kernels below follow the classic msun argument reductions and minimax/Taylor polynomials; after the
 // final rounding to f32 they are within 1 ulp, the same contract as the f32::sin/cos/acos/exp/ln/powf the
 // reference calls (brdf.rs:101-102, :270; light.rs:28-34; common.rs:128-135; openpbr.rs:598, :802).
+// That bound is measured, against float64 libm and 120-bit mpmath, by tests/test_math_host.py (DESIGN.md §2 has the
+// maxima) on these domains: sincos |x| <= 2^20*pi/2 (see sincos_det), acos [-1, 1], exp [-103.98, 88.73], log every
+// finite positive f32, pow every pair with a finite normal result. tests/test_gpu_math.py pins the device bits.
 // CDNA4 runs f64 FMA/ADD/MUL at half the f32 vector rate, so a sincos costs ~20 DP ops: cheap next to
 // the BVH traversal that dominates a path vertex.
 #pragma once
@@ -71,11 +74,20 @@ __device__ __forceinline__ double kcos(double x) {
   const double r = C2 + z * C3;
   return ((1.0 + z * C0) + w * C1) + (w * z) * r;
 }
+// Accuracy domain: |x| <= 2^20 * pi/2 (~1.647e6). PIO2_HI has 33 significant bits, so fn * PIO2_HI is exact only
+// while fn < 2^20; beyond that the reduction loses bits (cos is 4096 ulp off by 1e7) and the result, though still
+// the same bits on host and device, carries no accuracy claim and may leave [-1, 1].
+// Out-of-domain rule: NaN gives (NaN, NaN); |x| >= 2^62, +-inf included, gives (sin, cos) = (0, 1) — an f32 that
+// large is a multiple of 2^39, its phase is not information. The guard also keeps the double -> integer conversion
+// of fn in range: out of range it is undefined in C, x86 and gfx950 answer differently (INT64_MIN vs saturation),
+// and an authored thin_film_thickness reaches it (thin_film_lambda). Bits for |x| < 2^62 are those of the unguarded form.
 __device__ __forceinline__ void sincos_det(float xf, float &s, float &c) {
   const double INV_PIO2 = 6.36619772367581382433e-01;
   const double PIO2_HI = 1.57079632673412561417e+00;
   const double PIO2_LO = 6.07710050650619224932e-11;
   const double x = (double)xf;
+  if (x != x) { s = xf; c = xf; return; }
+  if (!((x < 0.0 ? -x : x) < 4611686018427387904.0)) { s = 0.0f; c = 1.0f; return; }
   const double fn = rint(x * INV_PIO2);
   const double y = (x - fn * PIO2_HI) - fn * PIO2_LO;
   const int n = (int)(long long)fn;

@@ -14,7 +14,10 @@
  * the same sequence (the HIP kernels) reproduces them bit for bit. Accuracy
  * is < 1 ulp in f32 after the final rounding, i.e. the same contract as Rust's
  * f32::sin & co. that the reference calls (brdf.rs:101-102, light.rs:28-34,
- * common.rs:128-135).
+ * common.rs:128-135). The bound is asserted against float64 libm and mpmath by
+ * tests/test_math_host.py on: sincos |x| <= 2^20*pi/2, acos [-1, 1], exp
+ * [-103.98, 88.73], log every finite positive f32, pow every pair with a
+ * finite normal result (measured maxima: DESIGN.md section 2).
  *
  * Vector helpers restate glam 0.33 Vec3A semantics on SSE2 (the reference's
  * build, docs/simd.md:4-5): component-wise IEEE ops, dot = (x*x'+y*y')+z*z',
@@ -101,13 +104,24 @@ static inline double ora_kcos(double x) {
   return ((1.0 + z * C0) + w * C1) + (w * z) * r;
 }
 /* Simultaneous sinf/cosf. Arguments on the hot path are in [0, 2*pi] (phi =
- * 2*pi*u) or small thin-film phases; the two-term pi/2 reduction is exact to
- * double precision for |x| < 1e5. */
+ * 2*pi*u) or thin-film phases, which an authored thickness can make as large
+ * as it likes.
+ * Accuracy domain: |x| <= 2^20 * pi/2 (~1.647e6). PIO2_HI has 33 significant
+ * bits, so fn * PIO2_HI is exact only while fn < 2^20; beyond that the result
+ * is still one fixed sequence (same bits as the device) but carries no accuracy
+ * claim and may leave [-1, 1].
+ * Out-of-domain rule: NaN gives (NaN, NaN); |x| >= 2^62, +-inf included, gives
+ * (sin, cos) = (0, 1). The guard keeps the double -> integer conversion of fn
+ * in range (out of range it is undefined: x86 gives INT64_MIN, gfx950
+ * saturates). Bits for |x| < 2^62 are those of the unguarded form.
+ * Measured accuracy: tests/test_math_host.py, DESIGN.md section 2. */
 static inline void ora_sincosf(float xf, float *s, float *c) {
   const double INV_PIO2 = 6.36619772367581382433e-01;
   const double PIO2_HI = 1.57079632673412561417e+00;
   const double PIO2_LO = 6.07710050650619224932e-11;
   double x = (double)xf;
+  if (x != x) { *s = xf; *c = xf; return; }
+  if (!((x < 0.0 ? -x : x) < 4611686018427387904.0)) { *s = 0.0f; *c = 1.0f; return; }
   double fn = rint(x * INV_PIO2);
   double y = (x - fn * PIO2_HI) - fn * PIO2_LO;
   int n = (int)(long long)fn;

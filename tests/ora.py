@@ -338,6 +338,13 @@ def lib():
     return L
 
 
+def math_driver():
+    """The batched drivers over ora_math.h / ora_qmc.h (oracle/ora_mathdrv.c, ora_m_*): drv(name, *arrays) -> arrays.
+    The call shape is shared with the host and device builds of the device source (tests/math_drivers.py)."""
+    import math_drivers
+    return math_drivers.oracle()
+
+
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
 
