@@ -153,6 +153,7 @@ class CrtRayStats(C.Structure):
 ABI_SYMBOLS = [
     "crt_builder_new", "crt_builder_free", "crt_reserve", "crt_count", "crt_attach_triangles", "crt_attach_sphere",
     "crt_attach_instance", "crt_attach_empty", "crt_set_triangles", "crt_set_sphere", "crt_set_instance", "crt_commit",
+    "crt_attach_round_curves", "crt_set_round_curves",
     "crt_scene_retain", "crt_scene_release", "crt_scene_bounds", "crt_scene_geometry_count", "crt_scene_has_motion",
     "crt_scene_primitive_count", "crt_scene_primitive_breakdown", "crt_scene_unique_primitive_breakdown", "crt_scene_memory_footprint", "crt_scene_tree",
     "crt_shard_pixels", "crt_intersect1", "crt_occluded1", "crt_intersect_n", "crt_occluded_n", "crt_intersect_n_stats",
@@ -195,6 +196,8 @@ def lib():
     L.crt_attach_triangles.argtypes = [vp, fp, C.c_size_t, up, C.c_size_t, fp, C.c_size_t, C.c_uint32, up]
     L.crt_attach_sphere.argtypes = [vp, fp, C.c_float, C.c_uint32, up]
     L.crt_attach_instance.argtypes = [vp, vp, fp, fp, C.c_uint32, up]
+    L.crt_attach_round_curves.argtypes = [vp, fp, C.c_size_t, C.c_uint32, up]
+    L.crt_set_round_curves.argtypes = [vp, C.c_uint32, fp, C.c_size_t]
     L.crt_attach_empty.argtypes = [vp, C.c_uint32, up]
     L.crt_set_triangles.argtypes = [vp, C.c_uint32, fp, C.c_size_t, up, C.c_size_t, fp, C.c_size_t]
     L.crt_set_sphere.argtypes = [vp, C.c_uint32, fp, C.c_float]
@@ -486,7 +489,7 @@ def hits_to_host(d_hits):
 
 class SceneBuilder:
     """crust_rt::SceneBuilder (scene.rs:147-342). Geometry variants are the attach_* methods
-    (Geometry::TriangleMesh / Sphere / Instance, scene.rs:87-122)."""
+    (Geometry::TriangleMesh / Sphere / RoundCurves / Instance, scene.rs:87-122)."""
 
     def __init__(self):
         self.h = lib().crt_builder_new()
@@ -524,6 +527,22 @@ class SceneBuilder:
         gid = C.c_uint32()
         _check(lib().crt_attach_sphere(self.h, _fp(c), radius, mask, C.byref(gid)), "crt_attach_sphere")
         return gid.value
+
+    @staticmethod
+    def _segments(segments):
+        return np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 8)
+
+    def attach_round_curves(self, segments, mask=MASK_ALL):
+        """Geometry::RoundCurves (scene.rs:99-102): segments is (n, 8) float32, p0 r0 p1 r1 per sphere-swept cone; a hit's
+        prim_id is the segment's index."""
+        s = self._segments(segments)
+        gid = C.c_uint32()
+        _check(lib().crt_attach_round_curves(self.h, _fp(s), s.shape[0], mask, C.byref(gid)), "crt_attach_round_curves")
+        return gid.value
+
+    def set_round_curves(self, gid, segments):
+        s = self._segments(segments)
+        _check(lib().crt_set_round_curves(self.h, gid, _fp(s), s.shape[0]), "crt_set_round_curves")
 
     def attach_instance(self, scene, l2w=IDENTITY12, l2w_end=None, mask=MASK_ALL):
         a = np.ascontiguousarray(l2w, dtype=np.float32)

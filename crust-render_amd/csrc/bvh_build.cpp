@@ -484,6 +484,10 @@ Aabb prim_bbox(const Prim &p) {
       F3 r = f3(p.radius, p.radius, p.radius);
       return {p.center - r, p.center + r};
     }
+    case PRIM_CURVE: {                                       // prim.rs:202-206: the two end spheres' boxes, united
+      const F3 r0 = f3(p.radius, p.radius, p.radius), r1 = f3(p.radius1, p.radius1, p.radius1);
+      return {vmin(p.v0 - r0, p.v1 - r1), vmax(p.v0 + r0, p.v1 + r1)};
+    }
     default: return p.bounds;  // prim.rs:380-382
   }
 }

@@ -8,6 +8,7 @@
 #include <new>
 #include <stdexcept>
 #include <unordered_set>
+#include <vector>
 
 #include "crt_internal.h"
 
@@ -37,6 +38,26 @@ void fill_sphere(Geom &g, const float c[3], float r) {
   g = Geom{G_SPHERE, g.mask};
   g.center = f3(c[0], c[1], c[2]);
   g.radius = r;
+}
+// CRT_OK, or CRT_ERR_BAD_ARG with the reason in crt_last_error: the builder's boxes and the SAH cannot take a NaN or an
+// infinity (the reference aborts on them)
+int check_segments(const char *what, const CrtCurveSegment *segs, size_t n) {
+  for (size_t k = 0; k < n; k++) {
+    const float f[8] = {segs[k].p0[0], segs[k].p0[1], segs[k].p0[2], segs[k].r0, segs[k].p1[0], segs[k].p1[1], segs[k].p1[2], segs[k].r1};
+    for (int c = 0; c < 8; c++)
+      if (!std::isfinite(f[c])) {
+        set_error_text("%s: segment %zu has a non-finite %s", what, k, (c & 3) == 3 ? "radius" : "point");
+        return (int)CRT_ERR_BAD_ARG;
+      }
+  }
+  return (int)CRT_OK;
+}
+void fill_curves(Geom &g, const CrtCurveSegment *segs, size_t n) {
+  static_assert(sizeof(CrtCurveSegment) == 32, "scene.rs:15-23");
+  const float *f = reinterpret_cast<const float *>(segs);
+  std::vector<float> copy(f, f + (segs ? 8 * n : 0));
+  g = Geom{G_CURVES, g.mask};
+  g.segs = std::move(copy);
 }
 void fill_instance(Geom &g, CrtScene *scene, const float l2w[12], const float *l2w_end) {
   g = Geom{G_INSTANCE, g.mask};
@@ -114,6 +135,18 @@ int crt_attach_instance(CrtBuilder *b, CrtScene *scene, const float l2w[12], con
     return (int)CRT_OK;
   });
 }
+int crt_attach_round_curves(CrtBuilder *b, const CrtCurveSegment *segments, size_t n, uint32_t mask, uint32_t *geom_id_out) {
+  if (!b || (n && !segments)) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_attach_round_curves", [&] {
+    if (const int rc = check_segments("crt_attach_round_curves", segments, n)) return rc;
+    Geom g;
+    g.mask = mask;
+    fill_curves(g, segments, n);
+    b->b.geoms.push_back(std::move(g));
+    if (geom_id_out) *geom_id_out = uint32_t(b->b.geoms.size() - 1);
+    return (int)CRT_OK;
+  });
+}
 int crt_attach_empty(CrtBuilder *b, uint32_t mask, uint32_t *geom_id_out) {
   return crt_attach_triangles(b, nullptr, 0, nullptr, 0, nullptr, 0, mask, geom_id_out);
 }
@@ -134,6 +167,18 @@ int crt_set_sphere(CrtBuilder *b, uint32_t id, const float center[3], float radi
   if (id >= b->b.geoms.size()) return CRT_ERR_BAD_ID;
   fill_sphere(b->b.geoms[id], center, radius);
   return CRT_OK;
+}
+int crt_set_round_curves(CrtBuilder *b, uint32_t id, const CrtCurveSegment *segments, size_t n) {
+  if (!b || (n && !segments)) return CRT_ERR_BAD_ARG;
+  if (id >= b->b.geoms.size()) return CRT_ERR_BAD_ID;
+  return abi_guard("crt_set_round_curves", [&] {
+    if (const int rc = check_segments("crt_set_round_curves", segments, n)) return rc;
+    Geom g;  // built aside: the slot keeps its old geometry if an allocation fails
+    g.mask = b->b.geoms[id].mask;
+    fill_curves(g, segments, n);
+    b->b.geoms[id] = std::move(g);
+    return (int)CRT_OK;
+  });
 }
 int crt_set_instance(CrtBuilder *b, uint32_t id, CrtScene *scene, const float l2w[12], const float *l2w_end) {
   if (!b || !scene || !l2w) return CRT_ERR_BAD_ARG;
@@ -205,6 +250,7 @@ int crt_scene_primitive_breakdown(const CrtScene *s, size_t out[5]) {
   for (const Prim &p : s->p->bvh.prims) {
     if (p.kind == PRIM_TRI) out[0]++;
     else if (p.kind == PRIM_SPHERE) out[1]++;
+    else if (p.kind == PRIM_CURVE) out[2]++;
     else out[4]++;
   }
   return CRT_OK;
@@ -214,6 +260,7 @@ void accumulate_unique(const Scene &sc, std::unordered_set<const Scene *> &visit
   for (const Prim &p : sc.bvh.prims) {
     if (p.kind == PRIM_TRI) acc[0]++;
     else if (p.kind == PRIM_SPHERE) acc[1]++;
+    else if (p.kind == PRIM_CURVE) acc[2]++;
     else {
       acc[4]++;
       if (visited.insert(p.scene.get()).second) accumulate_unique(*p.scene, visited, acc);

@@ -73,7 +73,7 @@ struct alignas(16) Tri4 {
 };
 static_assert(sizeof(Tri4) == 192, "triangle.rs:182-196");
 
-enum PrimKind : uint32_t { PRIM_TRI = 0, PRIM_SPHERE = 1, PRIM_INSTANCE = 2 };
+enum PrimKind : uint32_t { PRIM_TRI = 0, PRIM_SPHERE = 1, PRIM_INSTANCE = 2, PRIM_CURVE = 3 };
 
 struct Scene;
 
@@ -86,6 +86,7 @@ struct Prim {
   F3 n0, n1, n2;
   F3 center;
   float radius;
+  float radius1;  // PRIM_CURVE (prim.rs:175-183): p0 = v0, p1 = v1, r0 = radius, r1 = radius1
   std::shared_ptr<Scene> scene;
   Affine l2w, w2l;
   Mat3 normal_mat;
@@ -118,6 +119,7 @@ struct DevPrim {  // 64 bytes
   uint32_t kind, geom_id, prim_id, mask;
   float d[12];  // tri: v0 v1 v2 (9) + [9]=smooth-normal slot (u32 bits, ~0 = none)
                 // sphere: center (3), radius | instance: [0] = instance slot (u32 bits)
+                // curve segment: p0 (3), r0, p1 (3), r1
 };
 static_assert(sizeof(DevPrim) == 64, "");
 
@@ -162,6 +164,11 @@ struct DevScene {
 // a sphere exists somewhere (its normal is computed at the hit and kept until emit), or instances nest deeper than one
 // level (a hit below the first level is taken to its parent's space at exit). kColdTime: a moving instance exists.
 enum : uint32_t { kColdUV = 1u, kColdNormal = 2u, kColdTime = 4u, kColdAll = 7u };
+// Outside kColdAll, a bit of DevScene::cold AND of the kernels' cold argument: some tree of the image holds a round
+// curve segment (PRIM_CURVE). Only kernel instances built with it carry the rounded-cone arm of the scalar-primitive
+// phase (traverse_pool.hip.h) — three-wave instances all; every other instance is compiled exactly as without curves.
+// A curve's normal is computed at the hit and kept until emit, so the bit implies kColdNormal.
+constexpr uint32_t kColdCurve = 16u;
 // A fourth bit of the KERNELS' cold argument (never of DevScene::cold): the image holds no Tri4 packet at all and carries
 // direct leaf words (a scene of analytic spheres: openpbr_showcase) — the kernel instance then holds ONE engine copy, the
 // direct one, without the packet phase's Woop test and without the per-ray shear constants (traverse_pool.hip.h, NOPK).
@@ -248,12 +255,15 @@ struct EngineSelect {
   uint32_t window = CRT_POOL_NODES;     // nodes staged in LDS per workgroup
   int ext_cold = (int)kColdAll;         // k_extend<., ., COLD>: none / the pending normal only / everything
   int path_cold = (int)kColdAll;        // k_path<., ., COLD> of simple scenes: none / everything
+  bool curve = false;      // the image holds curve segments: the three-wave instances with the rounded-cone arm (kColdCurve)
 };
 // want_wide: -1 = the scene's own preference (wide_split), 0 / 1 = asked for (CRT_WIDE, tests); renderer: the choice for
 // the renderer's kernels (the batched queries' differs on large trees, wide_split). CRT_OK, or
 // CRT_ERR_UNSUPPORTED when what was asked for cannot decode the image — nothing is launched then.
 inline int select_engine(const DevScene &s, int want_wide, EngineSelect &e, bool renderer = false) {
   const bool has_direct_words = s.direct_leaves != 0;
+  const bool curve = (s.cold & kColdCurve) != 0;
+  if (curve && want_wide > 0) return CRT_ERR_UNSUPPORTED;  // no four-wave instance carries the rounded-cone arm
   // the plain WIDE kernels carry no direct-leaf engine; their WIDE = 2 instances (the renderer's only) carry nothing else
   if (want_wide == 1 && has_direct_words) return CRT_ERR_UNSUPPORTED;
   if (want_wide == 2 && !(has_direct_words && renderer && CRT_DIRECT_LEAVES != 0 && CRT_WIDE_DIRECT_BUILD != 0)) return CRT_ERR_UNSUPPORTED;
@@ -261,8 +271,8 @@ inline int select_engine(const DevScene &s, int want_wide, EngineSelect &e, bool
   // instances that hold the direct engine copy only — an entry the root test rejects never touches the stack, so the
   // direct engine lives with the short LDS stack where the flat one (gauged at 1 985 against 1 977 on MedCity) did not:
   // PointInstancedMedCity 2 234 -> 2 285 Mray/s, openpbr_showcase 13 070 -> 14 045, a 32 761-instance city 2 599 -> 2 790.
-  const bool auto_wide_direct = want_wide < 0 && renderer && has_direct_words && CRT_DIRECT_LEAVES != 0 && CRT_WIDE_DIRECT_BUILD != 0;
-  e.wide = auto_wide_direct || (want_wide < 0 ? wide_split(s, renderer) : want_wide != 0);
+  const bool auto_wide_direct = !curve && want_wide < 0 && renderer && has_direct_words && CRT_DIRECT_LEAVES != 0 && CRT_WIDE_DIRECT_BUILD != 0;
+  e.wide = auto_wide_direct || (want_wide < 0 ? (!curve && wide_split(s, renderer)) : want_wide != 0);
   e.wide_direct = auto_wide_direct || want_wide == 2;
   e.direct = (!e.wide || e.wide_direct) && CRT_DIRECT_LEAVES != 0 && has_direct_words;
   if (has_direct_words && !e.direct) return CRT_ERR_UNSUPPORTED;      // (a build without the direct form never writes one)
@@ -276,6 +286,8 @@ inline int select_engine(const DevScene &s, int want_wide, EngineSelect &e, bool
   e.path_cold = cold == 0 ? 0 : (int)kColdAll;
   // a packet-free image with direct words: the fused kernel's packet-free instance (general materials; pathtrace.hip)
   if (CRT_NOPK_BUILD && s.n_packets == 0 && e.direct) e.path_cold = (int)(kColdAll | kNoPackets);
+  e.curve = curve;
+  if (curve) e.ext_cold = e.path_cold = (int)(kColdAll | kColdCurve);  // one instance each: everything + the arm
   return CRT_OK;
 }
 // The check every launch site makes on the EngineSelect it was handed (defence in depth: select_engine already
@@ -284,7 +296,8 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
   if (s.direct_leaves != 0 && ((e.wide && !e.wide_direct) || !e.direct)) return false;
   if (e.wide_direct && s.direct_leaves == 0) return false;
   if ((kernel_cold & (int)kNoPackets) && (s.n_packets != 0 || s.direct_leaves == 0)) return false;  // a packet-free instance on packets
-  return ((int)(s.cold & kColdAll) & ~kernel_cold) == 0;
+  if ((s.cold & kColdCurve) && (e.wide || !e.curve)) return false;  // a curve image on an instance without the arm
+  return ((int)(s.cold & (kColdAll | kColdCurve)) & ~kernel_cold) == 0;
 }
 // CRT_WIDE (A/B runs, tests): 1 asks for the four-wave kernels, 0 for the three-wave ones. A request the image cannot
 // take falls back to the scene's own preference — the knob sweeps whole test sets, direct-leaf scenes included.
@@ -341,7 +354,7 @@ int scene_image_check(const Scene &scene, uint64_t out[8]);
 // Host-only: select_engine on the image this scene would upload, verified against a census of the image (scene.cpp).
 int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]);
 
-enum GeomKind { G_MESH, G_SPHERE, G_INSTANCE };
+enum GeomKind { G_MESH, G_SPHERE, G_INSTANCE, G_CURVES };
 struct Geom {
   GeomKind kind = G_MESH;
   uint32_t mask = CRT_MASK_ALL;
@@ -351,6 +364,7 @@ struct Geom {
   std::vector<float> normals;
   F3 center{0, 0, 0};
   float radius = 0;
+  std::vector<float> segs;  // G_CURVES: 8 floats per segment, p0 r0 p1 r1 (scene.rs:15-23)
   std::shared_ptr<Scene> scene;
   Affine l2w{};
   bool has_end = false;

@@ -1304,7 +1304,8 @@ __global__ __launch_bounds__(kBlock, CRT_SHADE_WIDE_WAVES) void k_shade_pipe(Par
 }
 
 // ---- shadow: World::occluded (rt_world.rs:235-237) for the queue; unoccluded requests pay out ----
-template <bool STATS, int WIDE>
+// CURVE: kColdCurve in the instances that run curve images (the any-hit engine keeps no other cold state apart)
+template <bool STATS, int WIDE, int CURVE = 0>
 __device__ __forceinline__ void shadow_segment(const Params &P, const PathSoA &N, const ShadowSoA &Q, Counters *C,
                                                float4 *staging, CrtTravStats *tstats, uint32_t *engine_lds) {
   const uint32_t n = ((const volatile uint32_t *)C->shadow)[blockIdx.x];
@@ -1339,7 +1340,7 @@ __device__ __forceinline__ void shadow_segment(const Params &P, const PathSoA &N
       N.c[tg] = v;
     }
   };
-  run_traversal<true, STATS, WIDE, (int)kColdAll, WIDE != 0>(P.scene, engine_lds, 0.001f, err, st, fetch, emit, CRT_MASK_SHADOW);
+  run_traversal<true, STATS, WIDE, (int)kColdAll | CURVE, WIDE != 0>(P.scene, engine_lds, 0.001f, err, st, fetch, emit, CRT_MASK_SHADOW);
   if (err) atomicOr(&C->err, err);
   if (STATS) flush_stats(st, tstats, done);
 }
@@ -1348,6 +1349,13 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_SHADOW_WAVES) void k_shadow(
                                                                      float4 *staging, CrtTravStats *tstats) {
   __shared__ __attribute__((aligned(16))) uint32_t engine_lds[WIDE ? kEngineLdsWide : kEngineLdsDwords];
   shadow_segment<STATS, WIDE>(P, N, Q, C, staging, tstats, engine_lds);
+}
+// the three-wave instance with the rounded-cone arm: images that hold curve segments (DevScene::cold, kColdCurve)
+template <bool STATS>
+__global__ __launch_bounds__(kBlock, CRT_SHADOW_WAVES) void k_shadow_curve(Params P, PathSoA N, ShadowSoA Q, Counters *C,
+                                                                        float4 *staging, CrtTravStats *tstats) {
+  __shared__ __attribute__((aligned(16))) uint32_t engine_lds[kEngineLdsDwords];
+  shadow_segment<STATS, 0, (int)kColdCurve>(P, N, Q, C, staging, tstats, engine_lds);
 }
 
 // ---- the whole path loop of one wavefront batch in ONE launch. Queue segments are private to their workgroup at
@@ -1380,7 +1388,7 @@ __global__ __launch_bounds__(kBlock, CRT_EXTEND_WAVES) void k_path(Params P, Pat
     shade_segment<MATS, false, LIT, kArenaDwords, DRV>(P, S, N, H, Q, C, cur, staging, arena, false);
     __syncthreads();
     if (LIT) {
-      shadow_segment<false, false>(P, N, Q, C, staging, nullptr, arena);
+      shadow_segment<false, false, COLD & (int)kColdCurve>(P, N, Q, C, staging, nullptr, arena);
       __syncthreads();
     }
     cur = 1 - cur;
@@ -1786,10 +1794,12 @@ struct Renderer {
     // the cold per-ray state the scene can need (DevScene::cold) picks the closest-hit kernels' instance: none / the
     // pending normal only / everything for the per-stage k_extend, none / everything for the fused kernel of simple
     // scenes — decided by select_engine, with the image in hand; a launch the image cannot take is refused, never made
-    const int ext_cold = d_tstats ? (int)kColdAll : engine.ext_cold;
+    const bool curve = engine.curve;  // curve images: the three-wave instances with the rounded-cone arm, the general k_path
+    const int ext_cold = curve ? (int)(kColdAll | kColdCurve) : (d_tstats ? (int)kColdAll : engine.ext_cold);
     // (general material tables run the full-cold fused kernel — or its packet-free instance, for images without a Tri4 packet)
     const bool nopk = mats_kind != 0 && (engine.path_cold & (int)kNoPackets) != 0;
-    const int path_cold = mats_kind == 0 ? (engine.path_cold & (int)kColdAll) : (int)(kColdAll | (nopk ? kNoPackets : 0u));
+    const int path_cold = curve ? (int)(kColdAll | kColdCurve)
+                                : (mats_kind == 0 ? (engine.path_cold & (int)kColdAll) : (int)(kColdAll | (nopk ? kNoPackets : 0u)));
     {
       EngineSelect launched = engine;
       launched.wide = wide;  // the fused kernel is a three-wave kernel whatever the scene prefers
@@ -1808,9 +1818,9 @@ struct Renderer {
 #define CRT_PATH_D(M, L, CO, D) \
   hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0)
 #if CRT_NOPK_BUILD  // the packet-free instances exist only in builds that ask for them (A/B: profiles/README.md, round 4)
-#define CRT_PATH_NP(M, L) do { if (nopk) CRT_PATH(M, L, kColdAll | kNoPackets); else CRT_PATH(M, L, kColdAll); } while (0)
+#define CRT_PATH_NP(M, L) do { if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else if (nopk) CRT_PATH(M, L, kColdAll | kNoPackets); else CRT_PATH(M, L, kColdAll); } while (0)
 #else
-#define CRT_PATH_NP(M, L) CRT_PATH(M, L, kColdAll)
+#define CRT_PATH_NP(M, L) do { if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else CRT_PATH(M, L, kColdAll); } while (0)
 #endif
         switch (mats_kind * 2 + (lit ? 1 : 0)) {
           // simple-material tables: the instances that read the derived records (drv), or the raw ones (CRT_MAT_DERIVED=0)
@@ -1848,9 +1858,9 @@ struct Renderer {
 #define CRT_TAIL_D(M, L, CO, D) \
   hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, it, cur)
 #if CRT_NOPK_BUILD
-#define CRT_TAIL_NP(M, L) do { if (nopk) CRT_TAIL(M, L, kColdAll | kNoPackets); else CRT_TAIL(M, L, kColdAll); } while (0)
+#define CRT_TAIL_NP(M, L) do { if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else if (nopk) CRT_TAIL(M, L, kColdAll | kNoPackets); else CRT_TAIL(M, L, kColdAll); } while (0)
 #else
-#define CRT_TAIL_NP(M, L) CRT_TAIL(M, L, kColdAll)
+#define CRT_TAIL_NP(M, L) do { if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else CRT_TAIL(M, L, kColdAll); } while (0)
 #endif
           switch (mats_kind * 2 + (lit ? 1 : 0)) {
             case 0:
@@ -1875,7 +1885,8 @@ struct Renderer {
 #define CRT_EXTEND(ST, W, CO) \
   timed(0, st, [&] { hipLaunchKernelGGL((k_extend<ST, W, CO>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, it == 0 ? 1 : 0, d_tstats); })
       // (the stats build of a direct-leaf image counts on the three-wave kernels: the counters do not depend on the engine split)
-      if (d_tstats) { if (wide && !wdirect) CRT_EXTEND(true, 1, kColdAll); else CRT_EXTEND(true, 0, kColdAll); }
+      if (curve) { if (d_tstats) CRT_EXTEND(true, 0, kColdAll | kColdCurve); else CRT_EXTEND(false, 0, kColdAll | kColdCurve); }  // never wide
+      else if (d_tstats) { if (wide && !wdirect) CRT_EXTEND(true, 1, kColdAll); else CRT_EXTEND(true, 0, kColdAll); }
 #if CRT_WIDE_DIRECT_BUILD
       else if (wdirect) { if (ext_cold == 0) CRT_EXTEND(false, 2, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 2, kColdNormal); else CRT_EXTEND(false, 2, kColdAll); }
 #endif
@@ -1909,7 +1920,11 @@ struct Renderer {
       if (P.n_lights > 0 && P.strategy != CRT_STRATEGY_BSDF) {
 #define CRT_SHADOW(ST, W) \
   timed(2, st, [&] { hipLaunchKernelGGL((k_shadow<ST, W>), dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats ? d_tstats + 1 : nullptr); })
-        if (d_tstats) { if (wide && !wdirect) CRT_SHADOW(true, 1); else CRT_SHADOW(true, 0); }
+        if (curve) timed(2, st, [&] {
+          if (d_tstats) hipLaunchKernelGGL(k_shadow_curve<true>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats + 1);
+          else hipLaunchKernelGGL(k_shadow_curve<false>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, (CrtTravStats *)nullptr);
+        });
+        else if (d_tstats) { if (wide && !wdirect) CRT_SHADOW(true, 1); else CRT_SHADOW(true, 0); }
 #if CRT_WIDE_DIRECT_BUILD
         else if (wdirect) CRT_SHADOW(false, 2);
 #endif
@@ -2087,6 +2102,8 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
     for (size_t k = 0; k < n_materials; k++) simple = simple && material_class(materials[k]) <= 1;
     simple = simple && knobs.simple != 0;  // CRT_SIMPLE=0: the general instance (A/B, tests)
     r.mats_kind = r.has_media ? 2 : (simple ? 0 : 1);
+    // a curve image runs the general instances: no simple-material k_path is built with the rounded-cone arm
+    if ((P.scene.cold & kColdCurve) && r.mats_kind == 0) r.mats_kind = 1;
   }
   P.materials = r.d_materials; P.mat_derived = r.d_mat_derived; P.lights = r.d_lights; P.pixel_index = r.d_pixels;
   P.mat_class = r.d_mat_class;

@@ -43,7 +43,10 @@ __device__ __forceinline__ bool lds_take(bool want, uint32_t *next, uint32_t lim
 }
 
 // WIDE: the four-workgroups-per-CU split of the engine (traverse_pool.hip.h), launched for flat scenes.
-template <bool STATS, bool WIDE>
+// COLD: the engine's cold fields, kColdAll — the batched queries report u and v — and, for curve images only,
+// kColdCurve: the engine with the rounded-cone arm (traverse_pool.hip.h). The curve instances are never WIDE. The other
+// instances come out of the compiler as they did before the parameter existed.
+template <bool STATS, bool WIDE, int COLD = (int)kColdAll>
 __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void intersect_n_kernel(DevScene S, const CrtRay *__restrict__ rays, size_t n,
                                                             float t_min, float t_max, CrtRayHit *__restrict__ hits,
                                                             uint32_t *__restrict__ err_out, CrtTravStats *stats) {
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void intersect_n_kernel(DevSc
   auto emit = [&](uint32_t k, bool hit, const Hit &h, float dx, float dy, float dz) {
     const size_t i = dealt_ray(k);
     CrtRayHit out;
-    if (hit) {  // scene.rs:355-365
+    if (hit) { /* scene.rs:355-365 */
       const bool front = dot3(dx, dy, dz, h.nx, h.ny, h.nz) < 0.0f;
       out.t = h.t;
       out.normal[0] = front ? h.nx : -h.nx;
@@ -81,12 +84,12 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void intersect_n_kernel(DevSc
     hits[i] = out;
     done++;
   };
-  run_traversal<false, STATS, WIDE>(S, engine_lds, t_min, err, st, fetch, emit);
+  run_traversal<false, STATS, WIDE, COLD>(S, engine_lds, t_min, err, st, fetch, emit);
   if (err) atomicOr(err_out, err);
   if (STATS) flush_stats(st, stats, done);
 }
 
-template <bool STATS, bool WIDE>
+template <bool STATS, bool WIDE, int COLD = (int)kColdAll>
 __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void occluded_n_kernel(DevScene S, const CrtRay *__restrict__ rays, size_t n,
                                                            float t_min, float t_max, uint32_t *__restrict__ out,
                                                            uint32_t *__restrict__ err_out, CrtTravStats *stats) {
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void occluded_n_kernel(DevSce
     out[dealt_ray(k)] = occ ? 1u : 0u;
     done++;
   };
-  run_traversal<true, STATS, WIDE>(S, engine_lds, t_min, err, st, fetch, emit);
+  run_traversal<true, STATS, WIDE, COLD>(S, engine_lds, t_min, err, st, fetch, emit);
   if (err) atomicOr(err_out, err);
   if (STATS) flush_stats(st, stats, done);
 }
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void occluded_n_kernel(DevSce
 int query_engine(const DevScene &s, EngineSelect &e) {
   const int rc = select_engine_env(s, e);
   if (rc != CRT_OK) return rc;
-  if (!engine_accepts(e, s, (int)kColdAll)) {
+  if (!engine_accepts(e, s, (int)(kColdAll | (e.curve ? kColdCurve : 0u)))) {
     set_error_text("traversal launch refused: the selected engine instance (wide %d, direct %d) cannot decode this image (direct words %u)",
                    (int)e.wide, (int)e.direct, s.direct_leaves);
     return CRT_ERR_UNSUPPORTED;
@@ -154,8 +157,13 @@ int launch_intersect_n(const DevScene &s, const CrtRay *d_rays, size_t n, float 
 #define CRT_LAUNCH(ST, W)                                                                                             \
   hipLaunchKernelGGL((intersect_n_kernel<ST, W>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
                      t_max, d_hits, e, d_stats)
-  if (d_stats) { if (wide) CRT_LAUNCH(true, true); else CRT_LAUNCH(true, false); }
+#define CRT_LAUNCH_CURVE(ST)                                                                                          \
+  hipLaunchKernelGGL((intersect_n_kernel<ST, false, (int)(kColdAll | kColdCurve)>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
+                     t_max, d_hits, e, d_stats)
+  if (eng.curve) { if (d_stats) CRT_LAUNCH_CURVE(true); else CRT_LAUNCH_CURVE(false); }  // never wide (query_engine)
+  else if (d_stats) { if (wide) CRT_LAUNCH(true, true); else CRT_LAUNCH(true, false); }
   else { if (wide) CRT_LAUNCH(false, true); else CRT_LAUNCH(false, false); }
+#undef CRT_LAUNCH_CURVE
 #undef CRT_LAUNCH
   return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : CRT_ERR_NO_DEVICE;
 }
@@ -171,8 +179,13 @@ int launch_occluded_n(const DevScene &s, const CrtRay *d_rays, size_t n, float t
 #define CRT_LAUNCH(ST, W)                                                                                            \
   hipLaunchKernelGGL((occluded_n_kernel<ST, W>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
                      t_max, d_out, e, d_stats)
-  if (d_stats) { if (wide) CRT_LAUNCH(true, true); else CRT_LAUNCH(true, false); }
+#define CRT_LAUNCH_CURVE(ST)                                                                                         \
+  hipLaunchKernelGGL((occluded_n_kernel<ST, false, (int)(kColdAll | kColdCurve)>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
+                     t_max, d_out, e, d_stats)
+  if (eng.curve) { if (d_stats) CRT_LAUNCH_CURVE(true); else CRT_LAUNCH_CURVE(false); }  // never wide (query_engine)
+  else if (d_stats) { if (wide) CRT_LAUNCH(true, true); else CRT_LAUNCH(true, false); }
   else { if (wide) CRT_LAUNCH(false, true); else CRT_LAUNCH(false, false); }
+#undef CRT_LAUNCH_CURVE
 #undef CRT_LAUNCH
   return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : CRT_ERR_NO_DEVICE;
 }

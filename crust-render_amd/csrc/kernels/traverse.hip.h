@@ -188,6 +188,92 @@ __device__ __forceinline__ void tri_normal(const DevScene &S, uint32_t prim_abs,
   nx = x / len; ny = y / len; nz = z / len;
 }
 
+// Round curve segment: nearest boundary hit of the sphere-swept cone p0/r0 -> p1/r1 in [t_min, t_max] (curve.rs:17-93,
+// rounded_cone_intersect, statement for statement). Candidates are found with the normalised direction and range-tested
+// in its units, both ends inclusive; a later candidate replaces the best one only when strictly nearer; the winner
+// converts back to the caller's parameter. n: the outward normal. ANY: the first accepted candidate ends the search
+// (t and n are then not meaningful).
+template <bool ANY>
+__device__ __forceinline__ bool rounded_cone(float ox, float oy, float oz, float dx, float dy, float dz, float p0x, float p0y,
+                                             float p0z, float r0, float p1x, float p1y, float p1z, float r1, float t_min,
+                                             float t_max, float &t_out, float &nx, float &ny, float &nz) {
+  r0 = r0 > 1e-6f ? r0 : 1e-6f;  // f32::max
+  r1 = r1 > 1e-6f ? r1 : 1e-6f;
+  const float len = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+  if (len < 1e-20f) return false;
+  const float rdx = dx / len, rdy = dy / len, rdz = dz / len;
+  const float n_min = t_min * len, n_max = t_max * len;
+  const float bax = p1x - p0x, bay = p1y - p0y, baz = p1z - p0z;
+  const float oax = ox - p0x, oay = oy - p0y, oaz = oz - p0z;
+  const float obx = ox - p1x, oby = oy - p1y, obz = oz - p1z;
+  const float rr = r0 - r1;
+  const float m0 = dot3(bax, bay, baz, bax, bay, baz);
+  const float m1 = dot3(bax, bay, baz, oax, oay, oaz);
+  const float m2 = dot3(bax, bay, baz, rdx, rdy, rdz);
+  const float m3 = dot3(rdx, rdy, rdz, oax, oay, oaz);
+  const float m5 = dot3(oax, oay, oaz, oax, oay, oaz);
+  const float m6 = dot3(obx, oby, obz, rdx, rdy, rdz);
+  const float m7 = dot3(obx, oby, obz, obx, oby, obz);
+  bool found = false;
+  float best = 0.0f;
+  // consider(t, n) with the normal still unscaled: (x, y, z) / div for a cap; div == 0 marks the body, normalised
+  float ux = 0.0f, uy = 0.0f, uz = 0.0f, udiv = 1.0f;
+  auto accept = [&](float t) { return t >= n_min && t <= n_max && (!found || t < best); };
+  const float d2 = m0 - rr * rr;
+  if (d2 > 0.0f) {  // the cone body between the tangency circles, when neither sphere swallows the other
+    const float k2 = d2 - m2 * m2;
+    const float k1 = (d2 * m3 - m1 * m2) + (m2 * rr) * r0;
+    const float k0 = ((d2 * m5 - m1 * m1) + ((m1 * rr) * r0) * 2.0f) - (m0 * r0) * r0;
+    const float h = k1 * k1 - k0 * k2;
+    if (h >= 0.0f && absf(k2) > 1e-12f) {
+      const float sq = sqrtf(h);
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const float t = (k == 0 ? -k1 - sq : -k1 + sq) / k2;
+        const float y = (m1 - r0 * rr) + t * m2;
+        if (y > 0.0f && y < d2 && accept(t)) {
+          if (ANY) return true;
+          found = true; best = t; udiv = 0.0f;
+          ux = d2 * (oax + t * rdx) - bax * y;
+          uy = d2 * (oay + t * rdy) - bay * y;
+          uz = d2 * (oaz + t * rdz) - baz * y;
+        }
+      }
+    }
+  }
+  const float h0 = (m3 * m3 - m5) + r0 * r0;  // the cap spheres
+  if (h0 >= 0.0f) {
+    const float sq = sqrtf(h0);
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const float t = k == 0 ? -m3 - sq : -m3 + sq;
+      if (accept(t)) {
+        if (ANY) return true;
+        found = true; best = t; udiv = r0;
+        ux = oax + t * rdx; uy = oay + t * rdy; uz = oaz + t * rdz;
+      }
+    }
+  }
+  const float h1 = (m6 * m6 - m7) + r1 * r1;
+  if (h1 >= 0.0f) {
+    const float sq = sqrtf(h1);
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const float t = k == 0 ? -m6 - sq : -m6 + sq;
+      if (accept(t)) {
+        if (ANY) return true;
+        found = true; best = t; udiv = r1;
+        ux = obx + t * rdx; uy = oby + t * rdy; uz = obz + t * rdz;
+      }
+    }
+  }
+  if (!found) return false;
+  if (udiv == 0.0f) udiv = sqrtf(dot3(ux, uy, uz, ux, uy, uz));  // Vec3A::normalize: v / length
+  t_out = best / len;
+  nx = ux / udiv; ny = uy / udiv; nz = uz / udiv;
+  return true;
+}
+
 // glam Affine3A at a shutter time (prim.rs:285-331): lerp of the two placements, inverted.
 __device__ __forceinline__ void motion_w2l(const DevInstanceMotion &in, float time, float w2l[12]) {
   float m[12];

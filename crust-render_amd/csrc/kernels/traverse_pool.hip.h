@@ -133,6 +133,7 @@ __device__ __forceinline__ int wave_count(bool p) {
 // + 2 of the 28 registers of per-ray cold state a lane carries through every phase; a flat-shaded triangle scene with
 // one level of instances (cornellbox, the stress scene, PointInstancedMedCity) needs none of them, and without them the
 // four-wave kernel's 32 spilled registers are 0 (round 3: bench extend 87.8 -> 79.6 ms per step, MedCity +3.9 %).
+// kColdCurve (outside kColdAll): the scalar-primitive phase also carries the arm for round curve segments.
 template <bool ANY, bool STATS, int ROWS, bool DIRECT, bool LEAN, int COLD, bool UMASK, class Fetch, class Emit>
 __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's pool_lds_dwords<ROWS>() */, float t_min,
                               uint32_t umask /* UMASK: the ray mask of every ray of the launch */,
@@ -886,6 +887,24 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
                   aux |= 1u << level;
                   if (STATS) st.accepted++;
                 }
+              }
+            }
+          } else if ((COLD & (int)kColdCurve) != 0 && hd.x == PRIM_CURVE) {  // prim.rs:185-200, curve.rs:17-93
+            // only in the instances built for curve images (kColdCurve: crt_internal.h, select_engine)
+            const float4 s0 = *reinterpret_cast<const float4 *>(p->d), s1 = *reinterpret_cast<const float4 *>(p->d + 4);
+            float t, cnx, cny, cnz;
+            if (rounded_cone<ANY>(g0.x, g0.y, g0.z, dx, dy, dz, s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, t_min, closest,
+                                  t, cnx, cny, cnz)) {
+              if (ANY) occluded = true;
+              else {
+                closest = t;
+                f0[at(row)].w = t;
+                wr(side_n, row, 0, cnx); wr(side_n, row, 1, cny); wr(side_n, row, 2, cnz);
+                wr(side_n, row, 3, __uint_as_float(hd.z));  // prim_id: the segment's index
+                wr(best, row, B_BU, 0); wr(best, row, B_BV, 0); wr(best, row, B_BDEFER, kInvalid); wr(best, row, B_BGEOM, hd.y);
+                wr(best, row, B_BINST, kInvalid);
+                aux |= 1u << level;
+                if (STATS) st.accepted++;
               }
             }
           } else {

@@ -64,7 +64,7 @@ std::shared_ptr<Scene> commit(Builder &&b) {  // scene.rs:226-341
   auto scene = std::make_shared<Scene>();
   scene->n_geoms = uint32_t(b.geoms.size());
   size_t total = 0;
-  for (const Geom &g : b.geoms) total += g.kind == G_MESH ? g.idx.size() / 3 : 1;
+  for (const Geom &g : b.geoms) total += g.kind == G_MESH ? g.idx.size() / 3 : (g.kind == G_CURVES ? g.segs.size() / 8 : 1);
   std::vector<Prim> prims;
   prims.reserve(total);
   bool has_motion = false;
@@ -105,6 +105,23 @@ std::shared_ptr<Scene> commit(Builder &&b) {  // scene.rs:226-341
         p.center = g.center;
         p.radius = g.radius;
         prims.push_back(std::move(p));
+        break;
+      }
+      case G_CURVES: {  // scene.rs:277-289: one primitive per segment, prim_id = its index
+        const size_t ns = g.segs.size() / 8;
+        for (size_t k = 0; k < ns; k++) {
+          const float *sg = &g.segs[8 * k];
+          Prim p{};
+          p.kind = PRIM_CURVE;
+          p.geom_id = geom_id;
+          p.prim_id = uint32_t(k);
+          p.mask = g.mask;
+          p.v0 = f3(sg[0], sg[1], sg[2]);
+          p.radius = sg[3];
+          p.v1 = f3(sg[4], sg[5], sg[6]);
+          p.radius1 = sg[7];
+          prims.push_back(std::move(p));
+        }
         break;
       }
       case G_INSTANCE: {
@@ -301,6 +318,9 @@ Flat::Placed place(Flat &f, const Scene &s) {
       d.d[9] = u2f(slot);
     } else if (p.kind == PRIM_SPHERE) {
       d.d[0] = p.center.x; d.d[1] = p.center.y; d.d[2] = p.center.z; d.d[3] = p.radius;
+    } else if (p.kind == PRIM_CURVE) {
+      d.d[0] = p.v0.x; d.d[1] = p.v0.y; d.d[2] = p.v0.z; d.d[3] = p.radius;
+      d.d[4] = p.v1.x; d.d[5] = p.v1.y; d.d[6] = p.v1.z; d.d[7] = p.radius1;
     } else {
       DevInstance in{};
       put_affine(in.w2l, p.w2l);
@@ -504,6 +524,7 @@ int flatten_image(const Scene &scene, FlatImage &im) {
     uint32_t cold = 0;
     for (const DevPrim &d : f.prims) {
       if (d.kind == PRIM_SPHERE) cold |= kColdNormal;
+      if (d.kind == PRIM_CURVE) cold |= kColdNormal | kColdCurve;
       if (d.kind == PRIM_TRI && f2u(d.d[9]) != 0xFFFFFFFFu) cold |= kColdUV;
     }
     if (instance_levels(scene) > 1) cold |= kColdNormal;
@@ -601,6 +622,17 @@ int scene_image_check(const Scene &scene, uint64_t out[8]) {
   for (uint32_t e : f.indices) {
     if (e & kIndexInstance) { if ((e & ~kIndexInstance) >= f.instances.size()) return fail("list entry: instance slot", e, f.instances.size()); }
     else if (e >= f.prims.size()) return fail("list entry: primitive", e, f.prims.size());
+    else if (f.prims[e].kind == PRIM_INSTANCE) return fail("list entry: an instance named by its primitive record", e, 0);
+  }
+  {  // the kinds the scalar-primitive phase has an arm for, and the curve bit exactly when a curve exists
+    bool any_curve = false;
+    for (size_t k = 0; k < f.prims.size(); k++) {
+      const uint32_t kind = f.prims[k].kind;
+      if (kind != PRIM_TRI && kind != PRIM_SPHERE && kind != PRIM_INSTANCE && kind != PRIM_CURVE) return fail("primitive record of an unknown kind", k, kind);
+      any_curve |= kind == PRIM_CURVE;
+    }
+    if (any_curve != ((im.cold & kColdCurve) != 0)) return fail("the image's curve bit does not match its primitives", any_curve, im.cold);
+    if (any_curve && !(im.cold & kColdNormal)) return fail("a curve image without the pending normal", im.cold, 0);
   }
   uint64_t moving = 0;
   for (const auto &mv : f.moving) {
@@ -658,6 +690,7 @@ int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]) {
     }
   for (const DevPrim &d : im.f.prims) {
     if (d.kind == PRIM_SPHERE) need_cold |= kColdNormal;
+    if (d.kind == PRIM_CURVE) need_cold |= kColdNormal | kColdCurve;
     if (d.kind == PRIM_TRI && f2u(d.d[9]) != 0xFFFFFFFFu) need_cold |= kColdUV;
   }
   if (instance_levels(scene) > 1) need_cold |= kColdNormal;

@@ -381,7 +381,7 @@ DEFAULT_MATERIAL = {"_preset": "diffuse", "base_color": (0.5, 0.5, 0.5), "specul
 
 class SceneDesc:
     def __init__(self):
-        self.geoms = []      # dicts: kind mesh|sphere|instance, mask, material (dict of overrides), + data
+        self.geoms = []      # dicts: kind mesh|sphere|instance|curves, mask, material (dict of overrides), + data
         self.protos = []     # shared local-space meshes: dict(verts, idx)
         self.lights = []     # dicts: kind, geom_id, radiance, center/radius or origin/edge_u/edge_v/normal
         self.camera = None   # dict(lookfrom, lookat, vup, vfov_deg, aspect, aperture, focus_dist)
@@ -636,6 +636,9 @@ def load(path, width=None, height=None):
             elif prim.type == "PointInstancer":
                 parts.extend(nested_instancer_parts(prim, this_local, _ray_mask(prim), depth + 1))
                 continue  # its prototypes are reached through it, never drawn directly
+            elif prim.type == "BasisCurves":  # usd_import.rs:1487-1500 makes a part of it; this reader does not yet
+                import warnings
+                warnings.warn(f"BasisCurves {prim.path}: curves inside a prototype are not decoded, skipped")
             for c in composed_children(prim):
                 stack.append((c, this_local))
         return parts
@@ -761,6 +764,19 @@ def load(path, width=None, height=None):
             else:
                 desc.geoms.append(dict(kind="sphere", center=center, radius=radius, mask=_ray_mask(prim),
                                        material=_material_of(prim, by_path), name=prim.name))
+        elif t == "BasisCurves":  # emit_curves (usd_import.rs:2133-2170)
+            if prim.attr("type", "cubic") != "linear":
+                # CubicCurves are not built by this backend yet (crt.h, CRT_ERR_UNSUPPORTED): what the reader does not
+                # decode it names and skips
+                import warnings
+                warnings.warn(f"BasisCurves {prim.path}: cubic curves are not decoded, skipped")
+            else:
+                segs = _linear_curve_segments(prim)
+                if segs is not None and abs(float(_det4(world))) >= 1e-12:  # a non-invertible placement hides the prim
+                    # the segments stay in local space, committed as a scene of their own, placed by ONE instance
+                    desc.protos.append(dict(segments=segs))
+                    desc.geoms.append(dict(kind="instance", proto=len(desc.protos) - 1, l2w=affine12(world),
+                                           mask=_ray_mask(prim), material=_material_of(prim, by_path), name=prim.name))
         elif t == "Camera":
             if desc.camera is None:
                 desc.camera = _camera(prim, world, s)
@@ -850,6 +866,41 @@ def load(path, width=None, height=None):
     return desc
 
 
+def _linear_curve_segments(prim):
+    """curve_segments (usd_import.rs:1993-2093) for type = "linear": [n, 8] float32 rows p0 r0 p1 r1, one per pair of
+    consecutive points of a curve; None when points / curveVertexCounts are missing, the basis is not one USD knows, or
+    no segment results.
+    A width is a diameter: r = 0.5 * max(width, 1e-6); its interpolation is resolved from the array's length — per
+    vertex, per curve, else the first value. A count that overruns the points ends the prim there."""
+    pts, counts = prim.attr("points"), prim.attr("curveVertexCounts")
+    if pts is None or counts is None:
+        return None
+    if prim.attr("basis", "bezier") not in ("bezier", "bspline", "catmullRom"):
+        return None
+    pts = np.asarray(pts, dtype=np.float32).reshape(-1, 3)
+    counts = [int(c) for c in np.asarray(counts).reshape(-1)]
+    widths = prim.attr("widths")
+    widths = np.asarray([1.0] if widths is None else widths, dtype=np.float32).reshape(-1)
+    if widths.size == 0:
+        widths = np.ones(1, dtype=np.float32)
+
+    def radius(point, curve):
+        w = widths[point] if widths.size == len(pts) else (widths[curve] if widths.size == len(counts) else widths[0])
+        return f32(0.5) * max(f32(w), f32(1e-6))
+
+    rows, offset = [], 0
+    for ci, cnt in enumerate(counts):
+        if cnt < 0 or offset + cnt > len(pts):
+            break
+        for k in range(cnt - 1):
+            a, b = offset + k, offset + k + 1
+            rows.append([*pts[a], radius(a, ci), *pts[b], radius(b, ci)])
+        offset += cnt
+    if not rows:  # usd_import.rs:2118-2121: a prim that yields no segment emits nothing (no geometry id, no material slot)
+        return None
+    return np.asarray(rows, dtype=np.float32).reshape(-1, 8)
+
+
 def _camera(prim, world, settings):  # build_camera, usd_import.rs:2174-2220
     lookfrom = _xf_point(world, [(0.0, 0.0, 0.0)])[0]
     forward = _normalize(_xf_vec(world, (0.0, 0.0, -1.0)))
@@ -893,7 +944,9 @@ def build_world(desc, api, new_material):
     protos = []
     for p in desc.protos:  # MeshArena::committed_scene, usd_import.rs:891-909; local sphere parts :1462-1484
         b = api.SceneBuilder()
-        if "radius" in p:
+        if "segments" in p:  # a linear BasisCurves prim's segments, in its local space
+            b.attach_round_curves(p["segments"])
+        elif "radius" in p:
             b.attach_sphere(p.get("center", (0.0, 0.0, 0.0)), float(p["radius"]))
         elif "instances" in p:  # a nested instancer's sub-scene: earlier protos placed once per nested instance
             for it in p["instances"]:
@@ -910,6 +963,8 @@ def build_world(desc, api, new_material):
             b.attach_sphere(g["center"], float(g["radius"]), mask=g["mask"])
         elif g["kind"] == "instance":
             b.attach_instance(protos[g["proto"]], g["l2w"], g.get("l2w_end"), mask=g["mask"])
+        elif g["kind"] == "curves":  # round curve segments at the top level (hand-built descriptions; the reader instances them)
+            b.attach_round_curves(g["segments"], mask=g["mask"])
         else:
             b.attach_empty(mask=g["mask"])
         materials.append(fill_material(new_material(), g["material"]))
