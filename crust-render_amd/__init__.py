@@ -162,7 +162,7 @@ ABI_SYMBOLS = [
     "crt_film_read", "crt_film_clear", "crt_renderer_active_pixels", "crt_renderer_sample_counts", "crt_render_stats", "crt_renderer_profile", "crt_renderer_profile_read",
     "crt_render_samples_stats", "crt_version", "crt_last_error", "crt_device_info",
     "crt_scene_primitive_extents", "crt_scene_traversal_error", "crt_thread_release", "crt_renderer_shade_class_stats", "crt_renderer_pipeline", "crt_renderer_lanes", "crt_scene_image_check",
-    "crt_scene_engine_select",
+    "crt_scene_engine_select", "crt_scene_image_prims",
     "crt_material_scatter_n", "crt_material_eval_n", "crt_material_emitted_n", "crt_light_sample_n", "crt_light_pdf_n",
     "crt_light_escaped_n",
     "crt_shard_padded_count", "crt_gather_plan_new", "crt_gather_plan_free", "crt_gather_plan_padded_count",
@@ -220,6 +220,8 @@ def lib():
     L.crt_scene_memory_footprint.argtypes = [vp, C.POINTER(C.c_size_t)]
     if hasattr(L, "crt_scene_image_check"):  # absent from older A/B variant libraries
         L.crt_scene_image_check.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "crt_scene_image_prims"):  # absent from older A/B variant libraries
+        L.crt_scene_image_prims.argtypes = [vp, up, C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "crt_scene_engine_select"):  # absent from older A/B variant libraries
         L.crt_scene_engine_select.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32)]
     L.crt_scene_tree.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
@@ -403,6 +405,18 @@ class Scene:
         _check(lib().crt_scene_image_check(self.h, out), "crt_scene_image_check")
         return dict(zip(("nodes", "leaf_words_plain", "leaf_words_direct_index", "leaf_words_direct_instance", "instances",
                          "moving_instances", "staged_roots", "direct_leaves"), map(int, out)))
+
+    def image_prims(self):
+        """Host-only: the primitive records of the device image as uint32 words [n, 16] (crt.h, crt_scene_image_prims):
+        kind, geom_id, prim_id, mask, twelve data words. Needs no GPU."""
+        import numpy as np
+        n = C.c_size_t()
+        _check(lib().crt_scene_image_prims(self.h, None, 0, C.byref(n)), "crt_scene_image_prims")
+        out = np.zeros((n.value, 16), np.uint32)
+        if n.value:
+            _check(lib().crt_scene_image_prims(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)),
+                   "crt_scene_image_prims")
+        return out
 
     def engine_select(self, want_wide=-1):
         """Which traversal-engine instance the library selects for this scene's image (crt.h, crt_scene_engine_select;

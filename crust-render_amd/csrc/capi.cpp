@@ -284,6 +284,18 @@ int crt_scene_image_check(CrtScene *s, uint64_t out[8]) {
     return CRT_ERR_BAD_ARG;
   }
 }
+int crt_scene_image_prims(CrtScene *s, uint32_t *words16, size_t cap_prims, size_t *n_prims) {
+  if (!s || !n_prims || (cap_prims && !words16)) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_scene_image_prims", [&] {
+    std::vector<DevPrim> prims;
+    const int rc = scene_image_prims(*s->p, prims);
+    if (rc != CRT_OK) return rc;
+    *n_prims = prims.size();
+    const size_t n = prims.size() < cap_prims ? prims.size() : cap_prims;
+    if (n) std::memcpy(words16, prims.data(), n * sizeof(DevPrim));
+    return (int)CRT_OK;
+  });
+}
 int crt_scene_engine_select(CrtScene *s, int want_wide, uint32_t out[8]) {
   if (!s || !out) return CRT_ERR_BAD_ARG;
   try {

@@ -6,6 +6,7 @@
 #pragma once
 
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -117,11 +118,35 @@ void build_bvh(Bvh &out, std::vector<Prim> &&prims);  // bvh.rs:300-327
 // ---------------------------------------------------------------------------------------------
 struct DevPrim {  // 64 bytes
   uint32_t kind, geom_id, prim_id, mask;
-  float d[12];  // tri: v0 v1 v2 (9) + [9]=smooth-normal slot (u32 bits, ~0 = none)
+  float d[12];  // tri: v0 v1 v2 (9), then flat: [9..11] = its unit geometric normal (flat_tri_normal)
+                //                         smooth: [9] = shading-normal slot (u32 bits), [10] = kSmoothNormalTag
                 // sphere: center (3), radius | instance: [0] = instance slot (u32 bits)
                 // curve segment: p0 (3), r0, p1 (3), r1
 };
 static_assert(sizeof(DevPrim) == 64, "");
+// DevPrim::d[10] of a triangle with shading normals: a SIGNALLING NaN. flat_tri_normal cannot produce it — an IEEE
+// division returns a quiet NaN (bit 22 set) whatever its operands — so one word tells the two forms apart, and it is in
+// the 16 bytes (d[8..11]) the normal is read from anyway.
+constexpr uint32_t kSmoothNormalTag = 0x7fa5a5a5u;
+
+#if defined(__HIPCC__)
+#define CRT_HOST_DEVICE __host__ __device__
+#else
+#define CRT_HOST_DEVICE
+#endif
+// Unit geometric normal of a flat triangle (prim.rs:76-95): edges, cross product, sqrt of the dot product, three IEEE
+// divisions, in the reference's operation order (-ffp-contract=off). A constant of the committed triangle: evaluated
+// once per commit (scene.cpp, flatten_image) and stored in the primitive record; the kernels only read it. A zero-area
+// triangle yields whatever the divisions give (NaN or infinities); it is never emitted (Tri4::normal_ok).
+CRT_HOST_DEVICE inline void flat_tri_normal(const float v[9], float n[3]) {
+  const float e1x = v[3] - v[0], e1y = v[4] - v[1], e1z = v[5] - v[2];
+  const float e2x = v[6] - v[0], e2y = v[7] - v[1], e2z = v[8] - v[2];
+  const float x = e1y * e2z - e2y * e1z;
+  const float y = e1z * e2x - e2z * e1x;
+  const float z = e1x * e2y - e2x * e1y;
+  const float len = sqrtf((x * x + y * y) + z * z);
+  n[0] = x / len; n[1] = y / len; n[2] = z / len;
+}
 
 struct DevInstance {  // 64 bytes: what an instance entry reads (half a cache line; 40 000 placements stay L2-resident)
   float w2l[12];      // cached world-to-local at time 0 (prim.rs:266); its matrix3 transposed is the normal matrix (:267)
@@ -351,6 +376,8 @@ struct Scene : std::enable_shared_from_this<Scene> {
 // Host-only self-check of the image Scene::ensure_device would upload (scene.cpp): CRT_OK and eight counts, or
 // CRT_ERR_BAD_ARG with the broken invariant in crt_last_error.
 int scene_image_check(const Scene &scene, uint64_t out[8]);
+// Host-only: the image's primitive records (scene.cpp).
+int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out);
 // Host-only: select_engine on the image this scene would upload, verified against a census of the image (scene.cpp).
 int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]);
 

@@ -166,26 +166,26 @@ __device__ __forceinline__ bool tri_scalar(const RayCtx &r, const float *v /*9: 
 
 // Geometric or interpolated normal of a triangle primitive (prim.rs:76-95). The degenerate-sliver
 // rejection has already happened through Tri4::normal_ok / the explicit check at the call site.
+// A flat triangle's normal is a constant of the committed scene: the upload stores it in the record (crt_internal.h,
+// flat_tri_normal) and one 16-byte read fetches it — the edges, cross product, square root and three divisions
+// were a sixth of a closest hit's emit step, per ray. SMOOTH: the instance can meet shading normals (kColdUV); the
+// others hold no second arm.
+template <bool SMOOTH>
 __device__ __forceinline__ void tri_normal(const DevScene &S, uint32_t prim_abs, float u, float v, float &nx, float &ny,
                                            float &nz) {
   const DevPrim *p = &S.prims[prim_abs];
-  const uint32_t slot = __float_as_uint(p->d[9]);
-  float x, y, z;
-  if (slot != kInvalid) {
-    const float *n = S.normals + 9 * (size_t)slot;
+  const float4 q = *reinterpret_cast<const float4 *>(p->d + 8);  // v2.z | normal, or slot and kSmoothNormalTag
+  if (SMOOTH && __float_as_uint(q.z) == kSmoothNormalTag) {
+    const float *n = S.normals + 9 * (size_t)__float_as_uint(q.y);
     const float w = 1.0f - u - v;
-    x = (n[0] * w + n[3] * u) + n[6] * v;
-    y = (n[1] * w + n[4] * u) + n[7] * v;
-    z = (n[2] * w + n[5] * u) + n[8] * v;
+    const float x = (n[0] * w + n[3] * u) + n[6] * v;
+    const float y = (n[1] * w + n[4] * u) + n[7] * v;
+    const float z = (n[2] * w + n[5] * u) + n[8] * v;
+    const float len = sqrtf(dot3(x, y, z, x, y, z));
+    nx = x / len; ny = y / len; nz = z / len;
   } else {
-    const float e1x = p->d[3] - p->d[0], e1y = p->d[4] - p->d[1], e1z = p->d[5] - p->d[2];
-    const float e2x = p->d[6] - p->d[0], e2y = p->d[7] - p->d[1], e2z = p->d[8] - p->d[2];
-    x = e1y * e2z - e2y * e1z;
-    y = e1z * e2x - e2z * e1x;
-    z = e1x * e2y - e2x * e1y;
+    nx = q.y; ny = q.z; nz = q.w;
   }
-  const float len = sqrtf(dot3(x, y, z, x, y, z));
-  nx = x / len; ny = y / len; nz = z / len;
 }
 
 // Round curve segment: nearest boundary hit of the sphere-swept cone p0/r0 -> p1/r1 in [t_min, t_max] (curve.rs:17-93,

@@ -55,6 +55,12 @@ namespace dev {
 #ifndef CRT_RARE_MIN
 #define CRT_RARE_MIN 24
 #endif
+#ifndef CRT_LEAN_MASKS_RIDE
+#define CRT_LEAN_MASKS_RIDE 1  // lean packet step: `active` and `mask_and` are fetched with the vertices, one wait (0: masks first, A/B)
+#endif
+#ifndef CRT_HIT_LANE_DIV
+#define CRT_HIT_LANE_DIV 1  // packet step: 1 / det and its three products for the lanes that hit only (0: for all four, A/B)
+#endif
 // Stack entries per ray kept in LDS (deeper entries go to private memory) and nodes of the top of the tree staged in
 // LDS are two sides of one LDS budget, and the best split depends on the scene: a single-level scene rarely goes
 // deeper than six entries and profits from the node window; instance-heavy scenes stack the parent's entries under
@@ -618,8 +624,30 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
                 for (int l = 0; l < 4; l++)
                   if ((meta.x & (1u << l)) && (lane_mask[l] & rmask)) m |= 1u << l;
               }
+            } else if (CRT_LEAN_MASKS_RIDE) {
+              // Lean form (the 128-register kernels): `active` and `mask_and` ride with the vertex planes, the ids and
+              // the normal-ok bits — eleven loads and one 8-byte one requested together and waited for once. Nearly
+              // every packet is decided by mask_and (all its lanes visible to the ray); only otherwise are mask_or and
+              // the per-lane masks fetched, in a second trip. m is what the staged form below computes.
+              uint2 am;  // active, mask_and
+              auto load_lean = [&](const Tri4 *q) {
+                am = *reinterpret_cast<const uint2 *>(&q->active);
+                prim4 = *reinterpret_cast<const uint4 *>(q->prim);
+                normal_ok = q->normal_ok;
+                load_vertices(q);
+              };
+              if (pk_lds) { load_lean(pk_l); asm volatile("" : "+v"(A_x.x), "+v"(B_x.x), "+v"(C_x.x), "+v"(prim4.x), "+v"(am.x)); }
+              else load_lean(pk);
+              if (rmask & am.y) m = am.x;                                        // triangle.rs:257-271
+              else if ((rmask & (pk_lds ? pk_l->mask_or : pk->mask_or)) == 0) m = 0;
+              else {
+                m = 0;
+#pragma unroll
+                for (int l = 0; l < 4; l++)
+                  if ((am.x & (1u << l)) && ((pk_lds ? pk_l->masks[l] : pk->masks[l]) & rmask)) m |= 1u << l;
+              }
             } else {
-              // Staged form (the 128-register kernels): masks first, vertices and ids behind the mask test.
+              // Staged form: masks first, vertices and ids behind the mask test (CRT_LEAN_MASKS_RIDE=0, A/B builds).
               uint4 meta;  // active, mask_and, mask_or, masks[0]
               if (pk_lds) { meta = *reinterpret_cast<const uint4 *>(&pk_l->active); asm volatile("" : "+v"(meta.x)); }
               else meta = *reinterpret_cast<const uint4 *>(&pk->active);
@@ -657,7 +685,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
               const float vcx[4] = {C_x.x, C_x.y, C_x.z, C_x.w}, vcy[4] = {C_y.x, C_y.y, C_y.z, C_y.w},
                           vcz[4] = {C_z.x, C_z.y, C_z.z, C_z.w};
               uint32_t fallback = 0, hits = 0;
-              float ht[4], hu[4], hv[4];
+              float ht[4], hu[4], hv[4], hdet[4];
               const float entry_closest = closest;  // every lane range-tests against the packet-entry bound
 #pragma unroll
               for (int l = 0; l < 4; l++) {  // triangle.rs:284-347, one SIMD lane at a time
@@ -679,10 +707,16 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
                 const bool lane_on = (m >> l) & 1u;
                 if (lane_on && zero) fallback |= 1u << l;
                 if (lane_on && !zero && !(neg && pos) && det != 0.0f && in_range) hits |= 1u << l;
-                const float inv_det = 1.0f / det;
-                ht[l] = t_scaled * inv_det;
-                hu[l] = e1 * inv_det;
-                hv[l] = e2 * inv_det;
+                if (CRT_HIT_LANE_DIV) {
+                  // t, u, v are needed by the lanes in `hits` alone — usually none or one of the four, never by an
+                  // any-hit ray: the division and its three products wait for the accept loop below
+                  ht[l] = t_scaled; hu[l] = e1; hv[l] = e2; hdet[l] = det;
+                } else {
+                  const float inv_det = 1.0f / det;
+                  ht[l] = t_scaled * inv_det;
+                  hu[l] = e1 * inv_det;
+                  hv[l] = e2 * inv_det;
+                }
               }
               if (ANY) {
                 if (hits) occluded = true;
@@ -690,9 +724,14 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
 #pragma unroll
                 for (int l = 0; l < 4; l++) {  // bvh.rs:533-550
                   if (!((hits >> l) & 1u)) continue;
-                  if (ht[l] > closest) continue;               // strict: an exact tie goes to the later lane
+                  float t = ht[l], u = hu[l], v = hv[l];
+                  if (CRT_HIT_LANE_DIV) {
+                    const float inv_det = 1.0f / hdet[l];  // triangle.rs:339-343, the IEEE division
+                    t = t * inv_det; u = u * inv_det; v = v * inv_det;
+                  }
+                  if (t > closest) continue;               // strict: an exact tie goes to the later lane
                   if (!((normal_ok >> l) & 1u)) continue;  // prim.rs:81-83 degenerate sliver
-                  closest = ht[l]; bu = hu[l]; bv = hv[l];
+                  closest = t; bu = u; bv = v;
                   bdefer = prim_of[l];
                   accepted = true;
                   if (STATS) st.accepted++;
@@ -920,7 +959,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
                 const float e2x = p->d[6] - p->d[0], e2y = p->d[7] - p->d[1], e2z = p->d[8] - p->d[2];
                 const bool flat = (e1y * e2z - e2y * e1z) == 0.0f && (e1z * e2x - e2z * e1x) == 0.0f &&
                                   (e1x * e2y - e2x * e1y) == 0.0f;
-                if (!(flat && __float_as_uint(p->d[9]) == kInvalid)) {
+                if (!(flat && __float_as_uint(p->d[10]) != kSmoothNormalTag)) {
                   closest = t;
                   f0[at(row)].w = t;
                   wr(best, row, B_BU, __float_as_uint(u)); wr(best, row, B_BV, __float_as_uint(v)); wr(best, row, B_BDEFER, pi);
@@ -967,7 +1006,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
           uint32_t bprim;
           const uint32_t bdefer = rd(best, row, B_BDEFER);
           if (bdefer != kInvalid) {
-            tri_normal(S, bdefer, __uint_as_float(rd(best, row, B_BU)), __uint_as_float(rd(best, row, B_BV)), bnx, bny, bnz);
+            tri_normal<(COLD & (int)kColdUV) != 0>(S, bdefer, __uint_as_float(rd(best, row, B_BU)), __uint_as_float(rd(best, row, B_BV)), bnx, bny, bnz);
             bprim = S.prims[bdefer].prim_id;
           } else {
             bnx = rd(side_n, row, 0); bny = rd(side_n, row, 1); bnz = rd(side_n, row, 2);
@@ -1009,7 +1048,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
           hit.u = __uint_as_float(rd(best, row, B_BU)); hit.v = __uint_as_float(rd(best, row, B_BV));
           const uint32_t bdefer = rd(best, row, B_BDEFER);
           if (bdefer != kInvalid) {
-            tri_normal(S, bdefer, hit.u, hit.v, hit.nx, hit.ny, hit.nz);
+            tri_normal<(COLD & (int)kColdUV) != 0>(S, bdefer, hit.u, hit.v, hit.nx, hit.ny, hit.nz);
             const DevPrim *p = &S.prims[bdefer];
             hit.geom = p->geom_id; hit.prim = p->prim_id;
           } else {

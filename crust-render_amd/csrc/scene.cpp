@@ -309,13 +309,14 @@ Flat::Placed place(Flat &f, const Scene &s) {
     if (p.kind == PRIM_TRI) {
       const float v[9] = {p.v0.x, p.v0.y, p.v0.z, p.v1.x, p.v1.y, p.v1.z, p.v2.x, p.v2.y, p.v2.z};
       std::memcpy(d.d, v, sizeof v);
-      uint32_t slot = 0xFFFFFFFFu;
       if (p.has_normals) {
-        slot = uint32_t(f.normals.size() / 9);
+        d.d[9] = u2f(uint32_t(f.normals.size() / 9));
+        d.d[10] = u2f(kSmoothNormalTag);
         const float n[9] = {p.n0.x, p.n0.y, p.n0.z, p.n1.x, p.n1.y, p.n1.z, p.n2.x, p.n2.y, p.n2.z};
         f.normals.insert(f.normals.end(), n, n + 9);
+      } else {
+        flat_tri_normal(d.d, d.d + 9);  // a constant of the committed triangle: derived here, once, read at every hit
       }
-      d.d[9] = u2f(slot);
     } else if (p.kind == PRIM_SPHERE) {
       d.d[0] = p.center.x; d.d[1] = p.center.y; d.d[2] = p.center.z; d.d[3] = p.radius;
     } else if (p.kind == PRIM_CURVE) {
@@ -525,7 +526,7 @@ int flatten_image(const Scene &scene, FlatImage &im) {
     for (const DevPrim &d : f.prims) {
       if (d.kind == PRIM_SPHERE) cold |= kColdNormal;
       if (d.kind == PRIM_CURVE) cold |= kColdNormal | kColdCurve;
-      if (d.kind == PRIM_TRI && f2u(d.d[9]) != 0xFFFFFFFFu) cold |= kColdUV;
+      if (d.kind == PRIM_TRI && f2u(d.d[10]) == kSmoothNormalTag) cold |= kColdUV;
     }
     if (instance_levels(scene) > 1) cold |= kColdNormal;
     if (!f.moving.empty()) cold |= kColdTime;
@@ -634,6 +635,23 @@ int scene_image_check(const Scene &scene, uint64_t out[8]) {
     if (any_curve != ((im.cold & kColdCurve) != 0)) return fail("the image's curve bit does not match its primitives", any_curve, im.cold);
     if (any_curve && !(im.cold & kColdNormal)) return fail("a curve image without the pending normal", im.cold, 0);
   }
+  {  // a flat triangle carries its unit normal, a smooth one its slot behind the tag no division can produce
+    size_t n_smooth = 0;
+    for (size_t k = 0; k < f.prims.size(); k++) {
+      const DevPrim &d = f.prims[k];
+      if (d.kind != PRIM_TRI) continue;
+      if (f2u(d.d[10]) == kSmoothNormalTag) {
+        if ((size_t(f2u(d.d[9])) + 1) * 9 > f.normals.size()) return fail("a smooth triangle's normal slot", k, f2u(d.d[9]));
+        n_smooth++;
+        continue;
+      }
+      float n[3];
+      flat_tri_normal(d.d, n);
+      if (std::memcmp(n, d.d + 9, sizeof n) != 0) return fail("a flat triangle's stored normal is not its geometric normal", k, 0);
+    }
+    if ((n_smooth != 0) != ((im.cold & kColdUV) != 0) && !(read_knobs().cold & kColdUV))
+      return fail("the image's shading-normal bit does not match its triangles", n_smooth, im.cold);
+  }
   uint64_t moving = 0;
   for (const auto &mv : f.moving) {
     const DevInstance &in = f.instances[mv.first];
@@ -647,6 +665,16 @@ int scene_image_check(const Scene &scene, uint64_t out[8]) {
     if (!(f.instances[k].flags & 2u) && (f.instances[k].flags >> 2) != 0) return fail("a static instance carries a placement offset", k, 0);
   out[0] = f.nodes.size(); out[1] = n_plain; out[2] = n_dindex; out[3] = n_dinst;
   out[4] = f.instances.size(); out[5] = moving; out[6] = im.n_staged_roots; out[7] = im.direct ? 1 : 0;
+  return CRT_OK;
+}
+
+// Host-only: the primitive records of the image Scene::ensure_device would upload, 16 words each (tests compare a flat
+// triangle's stored normal with an evaluation of their own).
+int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out) {
+  FlatImage im;
+  const int rc = flatten_image(scene, im);
+  if (rc != CRT_OK) return rc;
+  out.swap(im.f.prims);
   return CRT_OK;
 }
 
@@ -691,7 +719,7 @@ int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]) {
   for (const DevPrim &d : im.f.prims) {
     if (d.kind == PRIM_SPHERE) need_cold |= kColdNormal;
     if (d.kind == PRIM_CURVE) need_cold |= kColdNormal | kColdCurve;
-    if (d.kind == PRIM_TRI && f2u(d.d[9]) != 0xFFFFFFFFu) need_cold |= kColdUV;
+    if (d.kind == PRIM_TRI && f2u(d.d[10]) == kSmoothNormalTag) need_cold |= kColdUV;
   }
   if (instance_levels(scene) > 1) need_cold |= kColdNormal;
   if (!im.f.moving.empty()) need_cold |= kColdTime;

@@ -145,6 +145,13 @@ int crt_scene_primitive_extents(const CrtScene *s, size_t *count, float *scene_d
  * instanced roots staged for the LDS window | 1 if direct leaves are on. CRT_ERR_BAD_ARG + crt_last_error on a broken
  * invariant. (No reference counterpart: the image is this library's own layout of scene.rs:226-340's commit.) */
 int crt_scene_image_check(CrtScene *s, uint64_t out[8]);
+/* Host-only: the primitive records of that image, 16 words (64 bytes) each, in image order: kind, geom_id, prim_id,
+ * mask, then twelve data words — a triangle's three vertices and, for a flat triangle, its stored unit geometric normal
+ * in words 13..15 (a triangle with shading normals holds their slot in word 13 and the tag 0x7fa5a5a5, a signalling NaN
+ * no division returns, in word 14). The image check verifies every stored normal against a fresh evaluation; this lets
+ * a caller do the same. n_prims receives the record count; at most cap_prims records are copied to words16 (which may
+ * be NULL when cap_prims is 0). */
+int crt_scene_image_prims(CrtScene *s, uint32_t *words16, size_t cap_prims, size_t *n_prims);
 /* Host-only (no GPU needed): which instance of the traversal engine this library selects for the image the scene would
  * upload — ONE function decides it for the renderer, the batched and the single-ray queries — verified against a census
  * of the image: the instance decodes every child word (the four-wave kernels carry no direct-leaf form) and keeps every
