@@ -153,7 +153,7 @@ class CrtRayStats(C.Structure):
 ABI_SYMBOLS = [
     "crt_builder_new", "crt_builder_free", "crt_reserve", "crt_count", "crt_attach_triangles", "crt_attach_sphere",
     "crt_attach_instance", "crt_attach_empty", "crt_set_triangles", "crt_set_sphere", "crt_set_instance", "crt_commit",
-    "crt_attach_round_curves", "crt_set_round_curves",
+    "crt_attach_round_curves", "crt_set_round_curves", "crt_attach_cubic_curves", "crt_set_cubic_curves",
     "crt_scene_retain", "crt_scene_release", "crt_scene_bounds", "crt_scene_geometry_count", "crt_scene_has_motion",
     "crt_scene_primitive_count", "crt_scene_primitive_breakdown", "crt_scene_unique_primitive_breakdown", "crt_scene_memory_footprint", "crt_scene_tree",
     "crt_shard_pixels", "crt_intersect1", "crt_occluded1", "crt_intersect_n", "crt_occluded_n", "crt_intersect_n_stats",
@@ -198,6 +198,8 @@ def lib():
     L.crt_attach_instance.argtypes = [vp, vp, fp, fp, C.c_uint32, up]
     L.crt_attach_round_curves.argtypes = [vp, fp, C.c_size_t, C.c_uint32, up]
     L.crt_set_round_curves.argtypes = [vp, C.c_uint32, fp, C.c_size_t]
+    L.crt_attach_cubic_curves.argtypes = [vp, fp, C.c_size_t, C.c_uint32, up]
+    L.crt_set_cubic_curves.argtypes = [vp, C.c_uint32, fp, C.c_size_t]
     L.crt_attach_empty.argtypes = [vp, C.c_uint32, up]
     L.crt_set_triangles.argtypes = [vp, C.c_uint32, fp, C.c_size_t, up, C.c_size_t, fp, C.c_size_t]
     L.crt_set_sphere.argtypes = [vp, C.c_uint32, fp, C.c_float]
@@ -503,7 +505,7 @@ def hits_to_host(d_hits):
 
 class SceneBuilder:
     """crust_rt::SceneBuilder (scene.rs:147-342). Geometry variants are the attach_* methods
-    (Geometry::TriangleMesh / Sphere / RoundCurves / Instance, scene.rs:87-122)."""
+    (Geometry::TriangleMesh / Sphere / RoundCurves / CubicCurves / Instance, scene.rs:87-122)."""
 
     def __init__(self):
         self.h = lib().crt_builder_new()
@@ -557,6 +559,22 @@ class SceneBuilder:
     def set_round_curves(self, gid, segments):
         s = self._segments(segments)
         _check(lib().crt_set_round_curves(self.h, gid, _fp(s), s.shape[0]), "crt_set_round_curves")
+
+    @staticmethod
+    def _spans(spans):
+        return np.ascontiguousarray(spans, dtype=np.float32).reshape(-1, 14)
+
+    def attach_cubic_curves(self, spans, mask=MASK_ALL):
+        """Geometry::CubicCurves (scene.rs:103-106): spans is (n, 14) float32, four Bezier control points then r0, r1 per
+        span; a hit's prim_id is the span's index."""
+        s = self._spans(spans)
+        gid = C.c_uint32()
+        _check(lib().crt_attach_cubic_curves(self.h, _fp(s), s.shape[0], mask, C.byref(gid)), "crt_attach_cubic_curves")
+        return gid.value
+
+    def set_cubic_curves(self, gid, spans):
+        s = self._spans(spans)
+        _check(lib().crt_set_cubic_curves(self.h, gid, _fp(s), s.shape[0]), "crt_set_cubic_curves")
 
     def attach_instance(self, scene, l2w=IDENTITY12, l2w_end=None, mask=MASK_ALL):
         a = np.ascontiguousarray(l2w, dtype=np.float32)
@@ -796,13 +814,14 @@ def scene_path(name):
 
 
 def load_usda(path, width=None, height=None, max_depth=None, rank=0, world=1, variance=0.0, min_spp=None, dist=None,
-              timings=None):
+              timings=None, cubic_curves=False):
     """Scene::from_usd (scene.rs / usd_import.rs:287-424) for the text sample scenes -> (Renderer, desc).
     `path` may also name a synthetic scene: "synthetic:city" or "synthetic:city:<side>" (synthetic.py).
     variance > 0 enables adaptive stopping (the scene files' own default is 0.05; 0 = every sample, the rule for
     comparable runs, scripts/check_images.sh:5-11). dist: the job's torch.distributed module — the file is then imported
     by rank 0 only and broadcast (shard.import_once). timings: a dict that receives `import_s` (this rank's share of the
-    import: parsing on rank 0, waiting for the broadcast elsewhere) and `commit_s` (build_world: every rank's own commit)."""
+    import: parsing on rank 0, waiting for the broadcast elsewhere) and `commit_s` (build_world: every rank's own commit).
+    cubic_curves: decode cubic BasisCurves prims into cubic spans (usda.load); off, they are warned about and skipped."""
     from . import usda, shard
     import sys
     import time
@@ -813,7 +832,7 @@ def load_usda(path, width=None, height=None, max_depth=None, rank=0, world=1, va
         kw = dict(side=int(parts[2])) if len(parts) > 2 else {}
         desc = getattr(synthetic, parts[1])(width or 640, height or 360, **kw)
     else:
-        desc = shard.import_once(path, width, height, dist)
+        desc = shard.import_once(path, width, height, dist, cubic_curves=cubic_curves)
     me = sys.modules[__name__]
     t1 = time.perf_counter()
     scene, materials, protos = usda.build_world(desc, me, default_material)

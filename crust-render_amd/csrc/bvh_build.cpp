@@ -488,8 +488,34 @@ Aabb prim_bbox(const Prim &p) {
       const F3 r0 = f3(p.radius, p.radius, p.radius), r1 = f3(p.radius1, p.radius1, p.radius1);
       return {vmin(p.v0 - r0, p.v1 - r1), vmax(p.v0 + r0, p.v1 + r1)};
     }
+    case PRIM_CUBIC: {                                       // prim.rs:246-253: the control points' hull -+ max(r0, r1)
+      const float rm = p.radius > p.radius1 ? p.radius : p.radius1;  // f32::max of finite radii
+      const F3 r = f3(rm, rm, rm);
+      return {vmin(vmin(vmin(p.v0, p.v1), p.v2), p.v3) - r, vmax(vmax(vmax(p.v0, p.v1), p.v2), p.v3) + r};
+    }
     default: return p.bounds;  // prim.rs:380-382
   }
+}
+
+uint32_t cubic_flatness_depth(const float cp[12], float max_width) {  // curve.rs:122-141
+  float l0 = 0.0f;
+  for (int a = 0; a < 3; a++) {
+    const float d0 = (cp[a] - cp[3 + a] * 2.0f) + cp[6 + a];
+    const float d1 = (cp[3 + a] - cp[6 + a] * 2.0f) + cp[9 + a];
+    const float m = sse_max(std::fabs(d0), std::fabs(d1));
+    l0 = a == 0 ? m : sse_max(l0, m);
+  }
+  if (l0 <= 0.0f || max_width <= 0.0f) return 0;
+  const float eps = max_width * 0.05f;
+  const float x = ((1.41421356237309504880f * 6.0f) * l0) / (8.0f * eps);
+  // floor(log2(x) * 0.5) without a logarithm: floor(floor(log2 x) / 2), and floor(log2 x) of a normal x >= 1 is its
+  // binary exponent. (A rounded log2f can answer the next integer where x lies an ulp or two below a power of 4.)
+  uint32_t bits;
+  std::memcpy(&bits, &x, 4);
+  const uint32_t biased = (bits >> 23) & 0xffu;
+  if (!(x >= 1.0f) || biased == 0xffu) return 0;  // x < 1, NaN, infinity (log2 not finite, or negative: floor().max(0))
+  const uint32_t depth = (biased - 127u) >> 1;
+  return depth < kMaxCubicDepth ? depth : kMaxCubicDepth;
 }
 
 void build_bvh(Bvh &out, std::vector<Prim> &&prims) {  // bvh.rs:300-327

@@ -59,6 +59,24 @@ void fill_curves(Geom &g, const CrtCurveSegment *segs, size_t n) {
   g = Geom{G_CURVES, g.mask};
   g.segs = std::move(copy);
 }
+int check_spans(const char *what, const CrtCubicCurveSegment *spans, size_t n) {  // as check_segments
+  static_assert(sizeof(CrtCubicCurveSegment) == 56, "scene.rs:70-80");
+  for (size_t k = 0; k < n; k++) {
+    const float *f = reinterpret_cast<const float *>(spans + k);
+    for (int c = 0; c < 14; c++)
+      if (!std::isfinite(f[c])) {
+        set_error_text("%s: span %zu has a non-finite %s", what, k, c >= 12 ? "radius" : "control point");
+        return (int)CRT_ERR_BAD_ARG;
+      }
+  }
+  return (int)CRT_OK;
+}
+void fill_cubics(Geom &g, const CrtCubicCurveSegment *spans, size_t n) {
+  const float *f = reinterpret_cast<const float *>(spans);
+  std::vector<float> copy(f, f + (spans ? 14 * n : 0));
+  g = Geom{G_CUBICS, g.mask};
+  g.segs = std::move(copy);
+}
 void fill_instance(Geom &g, CrtScene *scene, const float l2w[12], const float *l2w_end) {
   g = Geom{G_INSTANCE, g.mask};
   g.scene = scene->p;
@@ -147,6 +165,18 @@ int crt_attach_round_curves(CrtBuilder *b, const CrtCurveSegment *segments, size
     return (int)CRT_OK;
   });
 }
+int crt_attach_cubic_curves(CrtBuilder *b, const CrtCubicCurveSegment *spans, size_t n, uint32_t mask, uint32_t *geom_id_out) {
+  if (!b || (n && !spans)) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_attach_cubic_curves", [&] {
+    if (const int rc = check_spans("crt_attach_cubic_curves", spans, n)) return rc;
+    Geom g;
+    g.mask = mask;
+    fill_cubics(g, spans, n);
+    b->b.geoms.push_back(std::move(g));
+    if (geom_id_out) *geom_id_out = uint32_t(b->b.geoms.size() - 1);
+    return (int)CRT_OK;
+  });
+}
 int crt_attach_empty(CrtBuilder *b, uint32_t mask, uint32_t *geom_id_out) {
   return crt_attach_triangles(b, nullptr, 0, nullptr, 0, nullptr, 0, mask, geom_id_out);
 }
@@ -176,6 +206,18 @@ int crt_set_round_curves(CrtBuilder *b, uint32_t id, const CrtCurveSegment *segm
     Geom g;  // built aside: the slot keeps its old geometry if an allocation fails
     g.mask = b->b.geoms[id].mask;
     fill_curves(g, segments, n);
+    b->b.geoms[id] = std::move(g);
+    return (int)CRT_OK;
+  });
+}
+int crt_set_cubic_curves(CrtBuilder *b, uint32_t id, const CrtCubicCurveSegment *spans, size_t n) {
+  if (!b || (n && !spans)) return CRT_ERR_BAD_ARG;
+  if (id >= b->b.geoms.size()) return CRT_ERR_BAD_ID;
+  return abi_guard("crt_set_cubic_curves", [&] {
+    if (const int rc = check_spans("crt_set_cubic_curves", spans, n)) return rc;
+    Geom g;  // built aside: the slot keeps its old geometry if an allocation fails
+    g.mask = b->b.geoms[id].mask;
+    fill_cubics(g, spans, n);
     b->b.geoms[id] = std::move(g);
     return (int)CRT_OK;
   });
@@ -251,6 +293,7 @@ int crt_scene_primitive_breakdown(const CrtScene *s, size_t out[5]) {
     if (p.kind == PRIM_TRI) out[0]++;
     else if (p.kind == PRIM_SPHERE) out[1]++;
     else if (p.kind == PRIM_CURVE) out[2]++;
+    else if (p.kind == PRIM_CUBIC) out[3]++;
     else out[4]++;
   }
   return CRT_OK;
@@ -261,6 +304,7 @@ void accumulate_unique(const Scene &sc, std::unordered_set<const Scene *> &visit
     if (p.kind == PRIM_TRI) acc[0]++;
     else if (p.kind == PRIM_SPHERE) acc[1]++;
     else if (p.kind == PRIM_CURVE) acc[2]++;
+    else if (p.kind == PRIM_CUBIC) acc[3]++;
     else {
       acc[4]++;
       if (visited.insert(p.scene.get()).second) accumulate_unique(*p.scene, visited, acc);

@@ -74,7 +74,8 @@ struct alignas(16) Tri4 {
 };
 static_assert(sizeof(Tri4) == 192, "triangle.rs:182-196");
 
-enum PrimKind : uint32_t { PRIM_TRI = 0, PRIM_SPHERE = 1, PRIM_INSTANCE = 2, PRIM_CURVE = 3 };
+// PRIM_CUBIC_TAIL: only in the device image — the second 64-byte record of a cubic span, never named by a leaf list.
+enum PrimKind : uint32_t { PRIM_TRI = 0, PRIM_SPHERE = 1, PRIM_INSTANCE = 2, PRIM_CURVE = 3, PRIM_CUBIC = 4, PRIM_CUBIC_TAIL = 5 };
 
 struct Scene;
 
@@ -88,6 +89,8 @@ struct Prim {
   F3 center;
   float radius;
   float radius1;  // PRIM_CURVE (prim.rs:175-183): p0 = v0, p1 = v1, r0 = radius, r1 = radius1
+  F3 v3;          // PRIM_CUBIC (prim.rs:220-227): cp = v0 v1 v2 v3, r0 = radius, r1 = radius1
+  uint32_t depth; // PRIM_CUBIC: cubic_flatness_depth of the span, computed once at commit
   std::shared_ptr<Scene> scene;
   Affine l2w, w2l;
   Mat3 normal_mat;
@@ -111,6 +114,12 @@ struct Bvh {
 constexpr uint32_t kMaxInstanceLevels = 8;
 
 Aabb prim_bbox(const Prim &p);
+// flatness_depth (curve.rs:122-141) of a cubic span, cp = 12 floats, max_width = 2 * max(r0, r1) with the radii as
+// given: l0, eps and x = SQRT_2 * 6 * l0 / (8 * eps) in f32 in the reference's order, then clamp(floor(log2(x) / 2), 0,
+// 10) read exactly from x's binary exponent — no libm on the path. 0 when l0 <= 0, max_width <= 0, x is not finite or
+// x < 1. The one function that computes it: commit stores it in the span's record, the kernels read it and loop.
+uint32_t cubic_flatness_depth(const float cp[12], float max_width);
+constexpr uint32_t kMaxCubicDepth = 10;  // curve.rs:98 MAX_RECURSION_DEPTH
 void build_bvh(Bvh &out, std::vector<Prim> &&prims);  // bvh.rs:300-327
 
 // ---------------------------------------------------------------------------------------------
@@ -122,6 +131,7 @@ struct DevPrim {  // 64 bytes
                 //                         smooth: [9] = shading-normal slot (u32 bits), [10] = kSmoothNormalTag
                 // sphere: center (3), radius | instance: [0] = instance slot (u32 bits)
                 // curve segment: p0 (3), r0, p1 (3), r1
+                // cubic span: cp0 cp1 cp2 cp3 (12); the NEXT record (PRIM_CUBIC_TAIL, same header): r0, r1, depth (u32 bits)
 };
 static_assert(sizeof(DevPrim) == 64, "");
 // DevPrim::d[10] of a triangle with shading normals: a SIGNALLING NaN. flat_tri_normal cannot produce it — an IEEE
@@ -194,6 +204,10 @@ enum : uint32_t { kColdUV = 1u, kColdNormal = 2u, kColdTime = 4u, kColdAll = 7u 
 // phase (traverse_pool.hip.h) — three-wave instances all; every other instance is compiled exactly as without curves.
 // A curve's normal is computed at the hit and kept until emit, so the bit implies kColdNormal.
 constexpr uint32_t kColdCurve = 16u;
+// Outside kColdAll too: some tree of the image holds a cubic curve span (PRIM_CUBIC). It implies kColdCurve (and so
+// kColdNormal): the instances built with it carry the span's subdivision walk BESIDE the rounded-cone arm — twelve
+// more three-wave instances; a round-only curve image keeps the instances it had.
+constexpr uint32_t kColdCubic = 32u;
 // A fourth bit of the KERNELS' cold argument (never of DevScene::cold): the image holds no Tri4 packet at all and carries
 // direct leaf words (a scene of analytic spheres: openpbr_showcase) — the kernel instance then holds ONE engine copy, the
 // direct one, without the packet phase's Woop test and without the per-ray shear constants (traverse_pool.hip.h, NOPK).
@@ -281,6 +295,8 @@ struct EngineSelect {
   int ext_cold = (int)kColdAll;         // k_extend<., ., COLD>: none / the pending normal only / everything
   int path_cold = (int)kColdAll;        // k_path<., ., COLD> of simple scenes: none / everything
   bool curve = false;      // the image holds curve segments: the three-wave instances with the rounded-cone arm (kColdCurve)
+  bool cubic = false;      // ... and cubic spans: their instances with the subdivision walk as well (kColdCubic; implies curve)
+  int curve_cold() const { return (int)((curve ? kColdCurve : 0u) | (cubic ? kColdCubic : 0u)); }
 };
 // want_wide: -1 = the scene's own preference (wide_split), 0 / 1 = asked for (CRT_WIDE, tests); renderer: the choice for
 // the renderer's kernels (the batched queries' differs on large trees, wide_split). CRT_OK, or
@@ -312,7 +328,8 @@ inline int select_engine(const DevScene &s, int want_wide, EngineSelect &e, bool
   // a packet-free image with direct words: the fused kernel's packet-free instance (general materials; pathtrace.hip)
   if (CRT_NOPK_BUILD && s.n_packets == 0 && e.direct) e.path_cold = (int)(kColdAll | kNoPackets);
   e.curve = curve;
-  if (curve) e.ext_cold = e.path_cold = (int)(kColdAll | kColdCurve);  // one instance each: everything + the arm
+  e.cubic = curve && (s.cold & kColdCubic) != 0;
+  if (curve) e.ext_cold = e.path_cold = (int)kColdAll | e.curve_cold();  // one instance each: everything + the arm(s)
   return CRT_OK;
 }
 // The check every launch site makes on the EngineSelect it was handed (defence in depth: select_engine already
@@ -322,7 +339,8 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
   if (e.wide_direct && s.direct_leaves == 0) return false;
   if ((kernel_cold & (int)kNoPackets) && (s.n_packets != 0 || s.direct_leaves == 0)) return false;  // a packet-free instance on packets
   if ((s.cold & kColdCurve) && (e.wide || !e.curve)) return false;  // a curve image on an instance without the arm
-  return ((int)(s.cold & (kColdAll | kColdCurve)) & ~kernel_cold) == 0;
+  if ((s.cold & kColdCubic) && (e.wide || !e.cubic || !(s.cold & kColdCurve))) return false;  // ... without the span's walk
+  return ((int)(s.cold & (kColdAll | kColdCurve | kColdCubic)) & ~kernel_cold) == 0;
 }
 // CRT_WIDE (A/B runs, tests): 1 asks for the four-wave kernels, 0 for the three-wave ones. A request the image cannot
 // take falls back to the scene's own preference — the knob sweeps whole test sets, direct-leaf scenes included.
@@ -381,7 +399,7 @@ int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out);
 // Host-only: select_engine on the image this scene would upload, verified against a census of the image (scene.cpp).
 int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]);
 
-enum GeomKind { G_MESH, G_SPHERE, G_INSTANCE, G_CURVES };
+enum GeomKind { G_MESH, G_SPHERE, G_INSTANCE, G_CURVES, G_CUBICS };
 struct Geom {
   GeomKind kind = G_MESH;
   uint32_t mask = CRT_MASK_ALL;
@@ -392,6 +410,7 @@ struct Geom {
   F3 center{0, 0, 0};
   float radius = 0;
   std::vector<float> segs;  // G_CURVES: 8 floats per segment, p0 r0 p1 r1 (scene.rs:15-23)
+                            // G_CUBICS: 14 floats per span, cp0 cp1 cp2 cp3 r0 r1 (scene.rs:70-80)
   std::shared_ptr<Scene> scene;
   Affine l2w{};
   bool has_end = false;

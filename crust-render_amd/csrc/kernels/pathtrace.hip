@@ -1357,6 +1357,13 @@ __global__ __launch_bounds__(kBlock, CRT_SHADOW_WAVES) void k_shadow_curve(Param
   __shared__ __attribute__((aligned(16))) uint32_t engine_lds[kEngineLdsDwords];
   shadow_segment<STATS, 0, (int)kColdCurve>(P, N, Q, C, staging, tstats, engine_lds);
 }
+// ... and with the cubic span's walk beside it: images that hold cubic spans (kColdCubic)
+template <bool STATS>
+__global__ __launch_bounds__(kBlock, CRT_SHADOW_WAVES) void k_shadow_cubic(Params P, PathSoA N, ShadowSoA Q, Counters *C,
+                                                                        float4 *staging, CrtTravStats *tstats) {
+  __shared__ __attribute__((aligned(16))) uint32_t engine_lds[kEngineLdsDwords];
+  shadow_segment<STATS, 0, (int)(kColdCurve | kColdCubic)>(P, N, Q, C, staging, tstats, engine_lds);
+}
 
 // ---- the whole path loop of one wavefront batch in ONE launch. Queue segments are private to their workgroup at
 // every stage (generate, extend, shade and shadow of segment b all run in workgroup b), so nothing but a workgroup
@@ -1388,7 +1395,7 @@ __global__ __launch_bounds__(kBlock, CRT_EXTEND_WAVES) void k_path(Params P, Pat
     shade_segment<MATS, false, LIT, kArenaDwords, DRV>(P, S, N, H, Q, C, cur, staging, arena, false);
     __syncthreads();
     if (LIT) {
-      shadow_segment<false, false, COLD & (int)kColdCurve>(P, N, Q, C, staging, nullptr, arena);
+      shadow_segment<false, false, COLD & (int)(kColdCurve | kColdCubic)>(P, N, Q, C, staging, nullptr, arena);
       __syncthreads();
     }
     cur = 1 - cur;
@@ -1795,10 +1802,11 @@ struct Renderer {
     // pending normal only / everything for the per-stage k_extend, none / everything for the fused kernel of simple
     // scenes — decided by select_engine, with the image in hand; a launch the image cannot take is refused, never made
     const bool curve = engine.curve;  // curve images: the three-wave instances with the rounded-cone arm, the general k_path
-    const int ext_cold = curve ? (int)(kColdAll | kColdCurve) : (d_tstats ? (int)kColdAll : engine.ext_cold);
+    const bool cubic = engine.cubic;  // ... cubic images: their instances with the span's walk as well
+    const int ext_cold = curve ? (int)kColdAll | engine.curve_cold() : (d_tstats ? (int)kColdAll : engine.ext_cold);
     // (general material tables run the full-cold fused kernel — or its packet-free instance, for images without a Tri4 packet)
     const bool nopk = mats_kind != 0 && (engine.path_cold & (int)kNoPackets) != 0;
-    const int path_cold = curve ? (int)(kColdAll | kColdCurve)
+    const int path_cold = curve ? (int)kColdAll | engine.curve_cold()
                                 : (mats_kind == 0 ? (engine.path_cold & (int)kColdAll) : (int)(kColdAll | (nopk ? kNoPackets : 0u)));
     {
       EngineSelect launched = engine;
@@ -1818,9 +1826,9 @@ struct Renderer {
 #define CRT_PATH_D(M, L, CO, D) \
   hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0)
 #if CRT_NOPK_BUILD  // the packet-free instances exist only in builds that ask for them (A/B: profiles/README.md, round 4)
-#define CRT_PATH_NP(M, L) do { if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else if (nopk) CRT_PATH(M, L, kColdAll | kNoPackets); else CRT_PATH(M, L, kColdAll); } while (0)
+#define CRT_PATH_NP(M, L) do { if (cubic) CRT_PATH(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else if (nopk) CRT_PATH(M, L, kColdAll | kNoPackets); else CRT_PATH(M, L, kColdAll); } while (0)
 #else
-#define CRT_PATH_NP(M, L) do { if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else CRT_PATH(M, L, kColdAll); } while (0)
+#define CRT_PATH_NP(M, L) do { if (cubic) CRT_PATH(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else CRT_PATH(M, L, kColdAll); } while (0)
 #endif
         switch (mats_kind * 2 + (lit ? 1 : 0)) {
           // simple-material tables: the instances that read the derived records (drv), or the raw ones (CRT_MAT_DERIVED=0)
@@ -1858,9 +1866,9 @@ struct Renderer {
 #define CRT_TAIL_D(M, L, CO, D) \
   hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, it, cur)
 #if CRT_NOPK_BUILD
-#define CRT_TAIL_NP(M, L) do { if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else if (nopk) CRT_TAIL(M, L, kColdAll | kNoPackets); else CRT_TAIL(M, L, kColdAll); } while (0)
+#define CRT_TAIL_NP(M, L) do { if (cubic) CRT_TAIL(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else if (nopk) CRT_TAIL(M, L, kColdAll | kNoPackets); else CRT_TAIL(M, L, kColdAll); } while (0)
 #else
-#define CRT_TAIL_NP(M, L) do { if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else CRT_TAIL(M, L, kColdAll); } while (0)
+#define CRT_TAIL_NP(M, L) do { if (cubic) CRT_TAIL(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else CRT_TAIL(M, L, kColdAll); } while (0)
 #endif
           switch (mats_kind * 2 + (lit ? 1 : 0)) {
             case 0:
@@ -1885,7 +1893,8 @@ struct Renderer {
 #define CRT_EXTEND(ST, W, CO) \
   timed(0, st, [&] { hipLaunchKernelGGL((k_extend<ST, W, CO>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, it == 0 ? 1 : 0, d_tstats); })
       // (the stats build of a direct-leaf image counts on the three-wave kernels: the counters do not depend on the engine split)
-      if (curve) { if (d_tstats) CRT_EXTEND(true, 0, kColdAll | kColdCurve); else CRT_EXTEND(false, 0, kColdAll | kColdCurve); }  // never wide
+      if (cubic) { if (d_tstats) CRT_EXTEND(true, 0, kColdAll | kColdCurve | kColdCubic); else CRT_EXTEND(false, 0, kColdAll | kColdCurve | kColdCubic); }  // never wide
+      else if (curve) { if (d_tstats) CRT_EXTEND(true, 0, kColdAll | kColdCurve); else CRT_EXTEND(false, 0, kColdAll | kColdCurve); }  // never wide
       else if (d_tstats) { if (wide && !wdirect) CRT_EXTEND(true, 1, kColdAll); else CRT_EXTEND(true, 0, kColdAll); }
 #if CRT_WIDE_DIRECT_BUILD
       else if (wdirect) { if (ext_cold == 0) CRT_EXTEND(false, 2, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 2, kColdNormal); else CRT_EXTEND(false, 2, kColdAll); }
@@ -1920,7 +1929,11 @@ struct Renderer {
       if (P.n_lights > 0 && P.strategy != CRT_STRATEGY_BSDF) {
 #define CRT_SHADOW(ST, W) \
   timed(2, st, [&] { hipLaunchKernelGGL((k_shadow<ST, W>), dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats ? d_tstats + 1 : nullptr); })
-        if (curve) timed(2, st, [&] {
+        if (cubic) timed(2, st, [&] {
+          if (d_tstats) hipLaunchKernelGGL(k_shadow_cubic<true>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats + 1);
+          else hipLaunchKernelGGL(k_shadow_cubic<false>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, (CrtTravStats *)nullptr);
+        });
+        else if (curve) timed(2, st, [&] {
           if (d_tstats) hipLaunchKernelGGL(k_shadow_curve<true>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats + 1);
           else hipLaunchKernelGGL(k_shadow_curve<false>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, (CrtTravStats *)nullptr);
         });

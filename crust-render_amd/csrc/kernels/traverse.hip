@@ -44,7 +44,8 @@ __device__ __forceinline__ bool lds_take(bool want, uint32_t *next, uint32_t lim
 
 // WIDE: the four-workgroups-per-CU split of the engine (traverse_pool.hip.h), launched for flat scenes.
 // COLD: the engine's cold fields, kColdAll — the batched queries report u and v — and, for curve images only,
-// kColdCurve: the engine with the rounded-cone arm (traverse_pool.hip.h). The curve instances are never WIDE. The other
+// kColdCurve: the engine with the rounded-cone arm (traverse_pool.hip.h). The curve instances are never WIDE. kColdCubic
+// beside it (cubic images): the span's subdivision walk as well. The other
 // instances come out of the compiler as they did before the parameter existed.
 template <bool STATS, bool WIDE, int COLD = (int)kColdAll>
 __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void intersect_n_kernel(DevScene S, const CrtRay *__restrict__ rays, size_t n,
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void occluded_n_kernel(DevSce
 int query_engine(const DevScene &s, EngineSelect &e) {
   const int rc = select_engine_env(s, e);
   if (rc != CRT_OK) return rc;
-  if (!engine_accepts(e, s, (int)(kColdAll | (e.curve ? kColdCurve : 0u)))) {
+  if (!engine_accepts(e, s, (int)kColdAll | e.curve_cold())) {
     set_error_text("traversal launch refused: the selected engine instance (wide %d, direct %d) cannot decode this image (direct words %u)",
                    (int)e.wide, (int)e.direct, s.direct_leaves);
     return CRT_ERR_UNSUPPORTED;
@@ -157,10 +158,11 @@ int launch_intersect_n(const DevScene &s, const CrtRay *d_rays, size_t n, float 
 #define CRT_LAUNCH(ST, W)                                                                                             \
   hipLaunchKernelGGL((intersect_n_kernel<ST, W>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
                      t_max, d_hits, e, d_stats)
-#define CRT_LAUNCH_CURVE(ST)                                                                                          \
-  hipLaunchKernelGGL((intersect_n_kernel<ST, false, (int)(kColdAll | kColdCurve)>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
+#define CRT_LAUNCH_CURVE(ST, CO)                                                                                        \
+  hipLaunchKernelGGL((intersect_n_kernel<ST, false, (int)(kColdAll | kColdCurve | (CO))>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
                      t_max, d_hits, e, d_stats)
-  if (eng.curve) { if (d_stats) CRT_LAUNCH_CURVE(true); else CRT_LAUNCH_CURVE(false); }  // never wide (query_engine)
+  if (eng.cubic) { if (d_stats) CRT_LAUNCH_CURVE(true, kColdCubic); else CRT_LAUNCH_CURVE(false, kColdCubic); }  // never wide (query_engine)
+  else if (eng.curve) { if (d_stats) CRT_LAUNCH_CURVE(true, 0u); else CRT_LAUNCH_CURVE(false, 0u); }
   else if (d_stats) { if (wide) CRT_LAUNCH(true, true); else CRT_LAUNCH(true, false); }
   else { if (wide) CRT_LAUNCH(false, true); else CRT_LAUNCH(false, false); }
 #undef CRT_LAUNCH_CURVE
@@ -179,10 +181,11 @@ int launch_occluded_n(const DevScene &s, const CrtRay *d_rays, size_t n, float t
 #define CRT_LAUNCH(ST, W)                                                                                            \
   hipLaunchKernelGGL((occluded_n_kernel<ST, W>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
                      t_max, d_out, e, d_stats)
-#define CRT_LAUNCH_CURVE(ST)                                                                                         \
-  hipLaunchKernelGGL((occluded_n_kernel<ST, false, (int)(kColdAll | kColdCurve)>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
+#define CRT_LAUNCH_CURVE(ST, CO)                                                                                       \
+  hipLaunchKernelGGL((occluded_n_kernel<ST, false, (int)(kColdAll | kColdCurve | (CO))>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, s, d_rays, n, t_min, \
                      t_max, d_out, e, d_stats)
-  if (eng.curve) { if (d_stats) CRT_LAUNCH_CURVE(true); else CRT_LAUNCH_CURVE(false); }  // never wide (query_engine)
+  if (eng.cubic) { if (d_stats) CRT_LAUNCH_CURVE(true, kColdCubic); else CRT_LAUNCH_CURVE(false, kColdCubic); }  // never wide (query_engine)
+  else if (eng.curve) { if (d_stats) CRT_LAUNCH_CURVE(true, 0u); else CRT_LAUNCH_CURVE(false, 0u); }
   else if (d_stats) { if (wide) CRT_LAUNCH(true, true); else CRT_LAUNCH(true, false); }
   else { if (wide) CRT_LAUNCH(false, true); else CRT_LAUNCH(false, false); }
 #undef CRT_LAUNCH_CURVE

@@ -274,6 +274,88 @@ __device__ __forceinline__ bool rounded_cone(float ox, float oy, float oz, float
   return true;
 }
 
+// f32::max / f32::min (IEEE maxNum / minNum): a NaN operand is dropped, the other one returned — NOT the SSE operand
+// rule of Vec3A. AABB::hit (aabb.rs:34-35) meets it with the 0 * inf of an axis-parallel ray whose origin lies on a face.
+__device__ __forceinline__ float maxnum(float a, float b) { return a != a ? b : (b != b ? a : (a > b ? a : b)); }
+__device__ __forceinline__ float minnum(float a, float b) { return a != a ? b : (b != b ? a : (a < b ? a : b)); }
+
+// Cubic curve span: cubic_curve_intersect / subdivide_and_intersect (curve.rs:166-217) for the depth commit stored
+// (cubic_flatness_depth), statement for statement in f32. The recursion is walked WITHOUT a stack: the state is the
+// root's control points, the best t and a path word (level, index of the node among its level's 2^level); a node's
+// control points are derived again from the root by replaying the midpoint splits along its path (subdivide_bezier,
+// :104-112: the same operations on the same operands as the recursion's, so the same bits), its parameter range
+// [idx, idx + 1] * 2^-level is exact. Per node, in the recursion's order (first half, then second): radius = the larger
+// of the ends', bezier_bounds, AABB::hit against [t_min, best so far] (aabb.rs:24-42); at the leaf level the cone
+// (rounded_cone, unmodified) with the best so far as t_max — a hit there replaces the best unconditionally. The best so
+// far IS the recursion's cur_t_max at every node: a call's t_max is its parent's cur_t_max, and a half that finds
+// nothing leaves it alone. At most 2^(depth + 1) - 2 nodes, depth <= 10, counted — no float result can extend the loop.
+// A span of depth 0 is its root alone: the walk's one leaf, met without a box test (curve.rs:191-193), radii
+// radius_at(0) and radius_at(1). ANY: the first accepted cone ends the walk. About a dozen registers beside the twelve
+// control-point floats; no LDS.
+template <bool ANY>
+__device__ __forceinline__ bool cubic_span(float ox, float oy, float oz, float dx, float dy, float dz, const float (&cp)[12],
+                                           float r0, float r1, uint32_t depth, float t_min, float t_max, float &t_out,
+                                           float &nx, float &ny, float &nz) {
+  if (depth > kMaxCubicDepth) depth = kMaxCubicDepth;
+  const float dr = r1 - r0;  // radius_at(u) = r0 + (r1 - r0) * u — also at u = 0 and 1: r0 + (r1 - r0) need not be r1
+  const float o[3] = {ox, oy, oz};
+  const float inv[3] = {1.0f / dx, 1.0f / dy, 1.0f / dz};  // aabb.rs:26, the same for every box
+  bool found = false;
+  float cur = t_max;
+  // depth 0: the root itself is the one leaf, met without a box test (curve.rs:191-193) — the same cone call site
+  uint32_t level = depth == 0 ? 0u : 1u, idx = 0;
+  const uint32_t budget = depth == 0 ? 1u : (2u << depth) - 2u;
+  for (uint32_t visited = 0; visited < budget; visited++) {
+    float c[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) c[i] = cp[i];
+    for (uint32_t k = level; k-- > 0;) {
+      const bool second = ((idx >> k) & 1u) != 0;
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const float p01 = (c[a] + c[3 + a]) * 0.5f, p12 = (c[3 + a] + c[6 + a]) * 0.5f, p23 = (c[6 + a] + c[9 + a]) * 0.5f;
+        const float p012 = (p01 + p12) * 0.5f, p123 = (p12 + p23) * 0.5f;
+        const float p0123 = (p012 + p123) * 0.5f;
+        c[a] = second ? p0123 : c[a];
+        c[3 + a] = second ? p123 : p01;
+        c[6 + a] = second ? p23 : p012;
+        c[9 + a] = second ? c[9 + a] : p0123;
+      }
+    }
+    const float scale = __uint_as_float((127u - level) << 23);  // 2^-level
+    const float ra = r0 + dr * ((float)idx * scale), rb = r0 + dr * ((float)(idx + 1u) * scale);
+    const float radius = maxnum(ra, rb);
+    float lo = t_min, hi = cur;
+    bool inside = true;
+    if (level != 0) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      float mn = c[a] < c[3 + a] ? c[a] : c[3 + a], mx = c[a] > c[3 + a] ? c[a] : c[3 + a];  // Vec3A::min / max (minps / maxps)
+      mn = mn < c[6 + a] ? mn : c[6 + a]; mx = mx > c[6 + a] ? mx : c[6 + a];
+      mn = mn < c[9 + a] ? mn : c[9 + a]; mx = mx > c[9 + a] ? mx : c[9 + a];
+      float t0 = ((mn - radius) - o[a]) * inv[a], t1 = ((mx + radius) - o[a]) * inv[a];
+      if (inv[a] < 0.0f) { const float s = t0; t0 = t1; t1 = s; }
+      lo = maxnum(lo, t0);
+      hi = minnum(hi, t1);
+      if (inside && hi <= lo) inside = false;  // (the reference returns here; later axes cannot bring it back)
+    }
+    }
+    if (inside && level < depth) { level++; idx <<= 1; continue; }
+    if (inside) {
+      float t, ux, uy, uz;
+      if (rounded_cone<ANY>(ox, oy, oz, dx, dy, dz, c[0], c[1], c[2], ra, c[9], c[10], c[11], rb, t_min, cur, t, ux, uy, uz)) {
+        if (ANY) return true;
+        found = true; cur = t; nx = ux; ny = uy; nz = uz;
+      }
+    }
+    while (idx & 1u) { idx >>= 1; level--; }  // a second half is done: so is its parent
+    if (level == 0) break;
+    idx |= 1u;                                // the first half's sibling
+  }
+  t_out = cur;
+  return found;
+}
+
 // glam Affine3A at a shutter time (prim.rs:285-331): lerp of the two placements, inverted.
 __device__ __forceinline__ void motion_w2l(const DevInstanceMotion &in, float time, float w2l[12]) {
   float m[12];

@@ -140,6 +140,7 @@ __device__ __forceinline__ int wave_count(bool p) {
 // one level of instances (cornellbox, the stress scene, PointInstancedMedCity) needs none of them, and without them the
 // four-wave kernel's 32 spilled registers are 0 (round 3: bench extend 87.8 -> 79.6 ms per step, MedCity +3.9 %).
 // kColdCurve (outside kColdAll): the scalar-primitive phase also carries the arm for round curve segments.
+// kColdCubic (outside kColdAll, with kColdCurve): ... and the arm for cubic curve spans (cubic_span, traverse.hip.h).
 template <bool ANY, bool STATS, int ROWS, bool DIRECT, bool LEAN, int COLD, bool UMASK, class Fetch, class Emit>
 __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's pool_lds_dwords<ROWS>() */, float t_min,
                               uint32_t umask /* UMASK: the ray mask of every ray of the launch */,
@@ -940,6 +941,26 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
                 f0[at(row)].w = t;
                 wr(side_n, row, 0, cnx); wr(side_n, row, 1, cny); wr(side_n, row, 2, cnz);
                 wr(side_n, row, 3, __uint_as_float(hd.z));  // prim_id: the segment's index
+                wr(best, row, B_BU, 0); wr(best, row, B_BV, 0); wr(best, row, B_BDEFER, kInvalid); wr(best, row, B_BGEOM, hd.y);
+                wr(best, row, B_BINST, kInvalid);
+                aux |= 1u << level;
+                if (STATS) st.accepted++;
+              }
+            }
+          } else if ((COLD & (int)kColdCubic) != 0 && hd.x == PRIM_CUBIC) {  // prim.rs:229-244, curve.rs:166-217
+            // only in the instances built for cubic images (kColdCubic). The span's two records: four control points
+            // here, radii and the depth commit derived in the next one — five 16-byte loads, none depending on another
+            const float4 c0 = *reinterpret_cast<const float4 *>(p->d), c1 = *reinterpret_cast<const float4 *>(p->d + 4),
+                         c2 = *reinterpret_cast<const float4 *>(p->d + 8), tl = *reinterpret_cast<const float4 *>(p[1].d);
+            const float ccp[12] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w};
+            float t, cnx, cny, cnz;
+            if (cubic_span<ANY>(g0.x, g0.y, g0.z, dx, dy, dz, ccp, tl.x, tl.y, __float_as_uint(tl.z), t_min, closest, t, cnx, cny, cnz)) {
+              if (ANY) occluded = true;
+              else {
+                closest = t;
+                f0[at(row)].w = t;
+                wr(side_n, row, 0, cnx); wr(side_n, row, 1, cny); wr(side_n, row, 2, cnz);
+                wr(side_n, row, 3, __uint_as_float(hd.z));  // prim_id: the span's index
                 wr(best, row, B_BU, 0); wr(best, row, B_BV, 0); wr(best, row, B_BDEFER, kInvalid); wr(best, row, B_BGEOM, hd.y);
                 wr(best, row, B_BINST, kInvalid);
                 aux |= 1u << level;

@@ -64,7 +64,7 @@ std::shared_ptr<Scene> commit(Builder &&b) {  // scene.rs:226-341
   auto scene = std::make_shared<Scene>();
   scene->n_geoms = uint32_t(b.geoms.size());
   size_t total = 0;
-  for (const Geom &g : b.geoms) total += g.kind == G_MESH ? g.idx.size() / 3 : (g.kind == G_CURVES ? g.segs.size() / 8 : 1);
+  for (const Geom &g : b.geoms) total += g.kind == G_MESH ? g.idx.size() / 3 : (g.kind == G_CURVES ? g.segs.size() / 8 : (g.kind == G_CUBICS ? g.segs.size() / 14 : 1));
   std::vector<Prim> prims;
   prims.reserve(total);
   bool has_motion = false;
@@ -120,6 +120,27 @@ std::shared_ptr<Scene> commit(Builder &&b) {  // scene.rs:226-341
           p.radius = sg[3];
           p.v1 = f3(sg[4], sg[5], sg[6]);
           p.radius1 = sg[7];
+          prims.push_back(std::move(p));
+        }
+        break;
+      }
+      case G_CUBICS: {  // scene.rs:290-301: one primitive per span, prim_id = its index
+        const size_t ns = g.segs.size() / 14;
+        for (size_t k = 0; k < ns; k++) {
+          const float *sp = &g.segs[14 * k];
+          Prim p{};
+          p.kind = PRIM_CUBIC;
+          p.geom_id = geom_id;
+          p.prim_id = uint32_t(k);
+          p.mask = g.mask;
+          p.v0 = f3(sp[0], sp[1], sp[2]);
+          p.v1 = f3(sp[3], sp[4], sp[5]);
+          p.v2 = f3(sp[6], sp[7], sp[8]);
+          p.v3 = f3(sp[9], sp[10], sp[11]);
+          p.radius = sp[12];
+          p.radius1 = sp[13];
+          // curve.rs:174: the depth depends on the span alone — computed here, once, stored, read by the kernels
+          p.depth = cubic_flatness_depth(sp, 2.0f * (sp[12] > sp[13] ? sp[12] : sp[13]));
           prims.push_back(std::move(p));
         }
         break;
@@ -270,6 +291,13 @@ Flat::Placed place(Flat &f, const Scene &s) {
   const uint32_t node0 = uint32_t(f.nodes.size()), leaf0 = uint32_t(f.leaves.size());
   const uint32_t pkt0 = uint32_t(f.packets.size()), idx0 = uint32_t(f.indices.size());
   const uint32_t prim0 = uint32_t(f.prims.size());
+  // A cubic span takes TWO consecutive records (DevPrim: control points, then radii and depth), so a primitive's record
+  // is its index plus the spans before it. Without spans: index + prim0, as ever.
+  std::vector<uint32_t> rec(b.prims.size());
+  {
+    uint32_t next = prim0;
+    for (size_t i = 0; i < b.prims.size(); i++) { rec[i] = next; next += b.prims[i].kind == PRIM_CUBIC ? 2u : 1u; }
+  }
   for (WideNode n : b.wide) {
     for (int l = 0; l < 4; l++) {
       if (!(n.flags & (1u << l))) continue;
@@ -284,7 +312,7 @@ Flat::Placed place(Flat &f, const Scene &s) {
   }
   for (Tri4 p : b.packets) {
     for (int l = 0; l < 4; l++)
-      if (p.active & (1u << l)) p.prim[l] += prim0;
+      if (p.active & (1u << l)) p.prim[l] = rec[p.prim[l]];
     f.packets.push_back(p);
   }
   // Instance slots in the order of the scalar lists (= the builder's leaf order, spatially coherent): the placements
@@ -322,6 +350,13 @@ Flat::Placed place(Flat &f, const Scene &s) {
     } else if (p.kind == PRIM_CURVE) {
       d.d[0] = p.v0.x; d.d[1] = p.v0.y; d.d[2] = p.v0.z; d.d[3] = p.radius;
       d.d[4] = p.v1.x; d.d[5] = p.v1.y; d.d[6] = p.v1.z; d.d[7] = p.radius1;
+    } else if (p.kind == PRIM_CUBIC) {
+      const float cp[12] = {p.v0.x, p.v0.y, p.v0.z, p.v1.x, p.v1.y, p.v1.z, p.v2.x, p.v2.y, p.v2.z, p.v3.x, p.v3.y, p.v3.z};
+      std::memcpy(d.d, cp, sizeof cp);
+      f.prims.push_back(d);
+      d.kind = PRIM_CUBIC_TAIL;  // the record behind it: the same header, r0, r1, depth; no leaf list names it
+      std::memset(d.d, 0, sizeof d.d);
+      d.d[0] = p.radius; d.d[1] = p.radius1; d.d[2] = u2f(p.depth);
     } else {
       DevInstance in{};
       put_affine(in.w2l, p.w2l);
@@ -341,7 +376,7 @@ Flat::Placed place(Flat &f, const Scene &s) {
     f.prims.push_back(d);
   }
   for (uint32_t i : b.indices)  // scalar lists: primitives by index, instances by their record
-    f.indices.push_back(b.prims[i].kind == PRIM_INSTANCE ? (kIndexInstance | inst_slot[i]) : (i + prim0));
+    f.indices.push_back(b.prims[i].kind == PRIM_INSTANCE ? (kIndexInstance | inst_slot[i]) : rec[i]);
   Flat::Placed me{b.wide.empty() ? CRT_INVALID_ID : node0, b.packets.empty() ? 0u : 1u};
   f.placed.emplace(&s, me);
   return me;
@@ -526,6 +561,7 @@ int flatten_image(const Scene &scene, FlatImage &im) {
     for (const DevPrim &d : f.prims) {
       if (d.kind == PRIM_SPHERE) cold |= kColdNormal;
       if (d.kind == PRIM_CURVE) cold |= kColdNormal | kColdCurve;
+      if (d.kind == PRIM_CUBIC) cold |= kColdNormal | kColdCurve | kColdCubic;
       if (d.kind == PRIM_TRI && f2u(d.d[10]) == kSmoothNormalTag) cold |= kColdUV;
     }
     if (instance_levels(scene) > 1) cold |= kColdNormal;
@@ -624,14 +660,33 @@ int scene_image_check(const Scene &scene, uint64_t out[8]) {
     if (e & kIndexInstance) { if ((e & ~kIndexInstance) >= f.instances.size()) return fail("list entry: instance slot", e, f.instances.size()); }
     else if (e >= f.prims.size()) return fail("list entry: primitive", e, f.prims.size());
     else if (f.prims[e].kind == PRIM_INSTANCE) return fail("list entry: an instance named by its primitive record", e, 0);
+    else if (f.prims[e].kind == PRIM_CUBIC_TAIL) return fail("list entry: a cubic span's second record", e, 0);
   }
+  for (const Tri4 &p : f.packets)
+    for (int l = 0; l < 4; l++)
+      if ((p.active & (1u << l)) && (p.prim[l] >= f.prims.size() || f.prims[p.prim[l]].kind != PRIM_TRI)) return fail("a packet lane names a record that is no triangle", p.prim[l], l);
   {  // the kinds the scalar-primitive phase has an arm for, and the curve bit exactly when a curve exists
-    bool any_curve = false;
+    bool any_curve = false, any_cubic = false;
     for (size_t k = 0; k < f.prims.size(); k++) {
       const uint32_t kind = f.prims[k].kind;
+      if (kind == PRIM_CUBIC) {
+        // the span's side storage: the continuation record is present, behind it, and carries the depth commit derived
+        const DevPrim &d = f.prims[k];
+        if (k + 1 >= f.prims.size() || f.prims[k + 1].kind != PRIM_CUBIC_TAIL) return fail("a cubic span without its second record", k, f.prims.size());
+        const DevPrim &t = f.prims[k + 1];
+        if (t.geom_id != d.geom_id || t.prim_id != d.prim_id || t.mask != d.mask) return fail("a cubic span's second record names another primitive", k, t.prim_id);
+        const uint32_t depth = f2u(t.d[2]);
+        if (depth > kMaxCubicDepth || depth != cubic_flatness_depth(d.d, 2.0f * (t.d[0] > t.d[1] ? t.d[0] : t.d[1])))
+          return fail("a cubic span's stored depth is not its flatness depth", k, depth);
+        any_curve = any_cubic = true;
+        k++;  // the second record
+        continue;
+      }
+      if (kind == PRIM_CUBIC_TAIL) return fail("a second record without its cubic span", k, kind);
       if (kind != PRIM_TRI && kind != PRIM_SPHERE && kind != PRIM_INSTANCE && kind != PRIM_CURVE) return fail("primitive record of an unknown kind", k, kind);
       any_curve |= kind == PRIM_CURVE;
     }
+    if (any_cubic != ((im.cold & kColdCubic) != 0)) return fail("the image's cubic bit does not match its primitives", any_cubic, im.cold);
     if (any_curve != ((im.cold & kColdCurve) != 0)) return fail("the image's curve bit does not match its primitives", any_curve, im.cold);
     if (any_curve && !(im.cold & kColdNormal)) return fail("a curve image without the pending normal", im.cold, 0);
   }
@@ -719,6 +774,7 @@ int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]) {
   for (const DevPrim &d : im.f.prims) {
     if (d.kind == PRIM_SPHERE) need_cold |= kColdNormal;
     if (d.kind == PRIM_CURVE) need_cold |= kColdNormal | kColdCurve;
+    if (d.kind == PRIM_CUBIC) need_cold |= kColdNormal | kColdCurve | kColdCubic;
     if (d.kind == PRIM_TRI && f2u(d.d[10]) == kSmoothNormalTag) need_cold |= kColdUV;
   }
   if (instance_levels(scene) > 1) need_cold |= kColdNormal;

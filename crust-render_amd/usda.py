@@ -381,7 +381,7 @@ DEFAULT_MATERIAL = {"_preset": "diffuse", "base_color": (0.5, 0.5, 0.5), "specul
 
 class SceneDesc:
     def __init__(self):
-        self.geoms = []      # dicts: kind mesh|sphere|instance|curves, mask, material (dict of overrides), + data
+        self.geoms = []      # dicts: kind mesh|sphere|instance|curves|cubic_curves, mask, material (dict of overrides), + data
         self.protos = []     # shared local-space meshes: dict(verts, idx)
         self.lights = []     # dicts: kind, geom_id, radiance, center/radius or origin/edge_u/edge_v/normal
         self.camera = None   # dict(lookfrom, lookat, vup, vfov_deg, aspect, aperture, focus_dist)
@@ -483,9 +483,11 @@ def dome_light(tint):
     return dict(kind="dome", geom_id=0xFFFFFFFF, radiance=np.asarray(tint, dtype=np.float32))
 
 
-def load(path, width=None, height=None):
+def load(path, width=None, height=None, cubic_curves=False):
     """Reads a .usda file into a SceneDesc. width/height override the RenderSettings resolution BEFORE the
-    camera is built (the aspect ratio feeds Camera::new; the reference can only do this by editing the USD)."""
+    camera is built (the aspect ratio feeds Camera::new; the reference can only do this by editing the USD).
+    cubic_curves: decode cubic BasisCurves prims into cubic spans (Geometry::CubicCurves) as the reference's importer
+    does; by default they are named in a warning and skipped, as before the backend could trace them."""
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:6] == b"\xfd7zXZ\x00":  # an .xz-compressed stage (scenes/stress.usda.xz: 15 MB of generated text, 0.7 MB packed)
@@ -765,16 +767,25 @@ def load(path, width=None, height=None):
                 desc.geoms.append(dict(kind="sphere", center=center, radius=radius, mask=_ray_mask(prim),
                                        material=_material_of(prim, by_path), name=prim.name))
         elif t == "BasisCurves":  # emit_curves (usd_import.rs:2133-2170)
-            if prim.attr("type", "cubic") != "linear":
-                # CubicCurves are not built by this backend yet (crt.h, CRT_ERR_UNSUPPORTED): what the reader does not
-                # decode it names and skips
+            cubic = prim.attr("type", "cubic") != "linear"
+            if cubic and not cubic_curves:
+                # decoding cubic prims is opt-in (load(..., cubic_curves=True)): what the reader does not decode it names
+                # and skips
                 import warnings
                 warnings.warn(f"BasisCurves {prim.path}: cubic curves are not decoded, skipped")
             else:
-                segs = _linear_curve_segments(prim)
-                if segs is not None and abs(float(_det4(world))) >= 1e-12:  # a non-invertible placement hides the prim
+                # (a prim is of ONE type, so it yields one kind; were it ever both, both geometries would go under the one
+                # instance, round first: usd_import.rs:2150-2158 — build_world attaches them in that order)
+                segs = None if cubic else _linear_curve_segments(prim)
+                spans = _cubic_curve_spans(prim) if cubic else None
+                if (segs is not None or spans is not None) and abs(float(_det4(world))) >= 1e-12:  # a non-invertible placement hides the prim
                     # the segments stay in local space, committed as a scene of their own, placed by ONE instance
-                    desc.protos.append(dict(segments=segs))
+                    proto = {}
+                    if segs is not None:
+                        proto["segments"] = segs
+                    if spans is not None:
+                        proto["spans"] = spans
+                    desc.protos.append(proto)
                     desc.geoms.append(dict(kind="instance", proto=len(desc.protos) - 1, l2w=affine12(world),
                                            mask=_ray_mask(prim), material=_material_of(prim, by_path), name=prim.name))
         elif t == "Camera":
@@ -901,6 +912,69 @@ def _linear_curve_segments(prim):
     return np.asarray(rows, dtype=np.float32).reshape(-1, 8)
 
 
+# usd_import.rs:1914-1931, row-major [t^3 t^2 t 1] . M . [P0 P1 P2 P3]^T, entries evaluated in f32 as the reference writes them
+_BEZIER_M = [[f32(-1.0), f32(3.0), f32(-3.0), f32(1.0)], [f32(3.0), f32(-6.0), f32(3.0), f32(0.0)],
+             [f32(-3.0), f32(3.0), f32(0.0), f32(0.0)], [f32(1.0), f32(0.0), f32(0.0), f32(0.0)]]
+_BSPLINE_M = [[f32(-1.0) / f32(6.0), f32(3.0) / f32(6.0), f32(-3.0) / f32(6.0), f32(1.0) / f32(6.0)],
+              [f32(3.0) / f32(6.0), f32(-6.0) / f32(6.0), f32(3.0) / f32(6.0), f32(0.0)],
+              [f32(-3.0) / f32(6.0), f32(0.0), f32(3.0) / f32(6.0), f32(0.0)],
+              [f32(1.0) / f32(6.0), f32(4.0) / f32(6.0), f32(1.0) / f32(6.0), f32(0.0)]]
+_CATMULL_ROM_M = [[f32(-0.5), f32(1.5), f32(-1.5), f32(0.5)], [f32(1.0), f32(-2.5), f32(2.0), f32(-0.5)],
+                  [f32(-0.5), f32(0.0), f32(0.5), f32(0.0)], [f32(0.0), f32(1.0), f32(0.0), f32(0.0)]]
+_CUBIC_BASES = {"bezier": (_BEZIER_M, 3), "bspline": (_BSPLINE_M, 1), "catmullRom": (_CATMULL_ROM_M, 1)}
+
+
+def _basis_to_bezier(m, cp):
+    """basis_to_bezier (usd_import.rs:1962-1976) in float32, operation for operation: cp (4, 3) float32 in the basis m ->
+    the Bezier control points of the same curve."""
+    def coeff(row):
+        s = np.zeros(3, np.float32)
+        for c in range(4):
+            s = s + cp[c] * m[row][c]
+        return s
+    a, b, c, d = coeff(0), coeff(1), coeff(2), coeff(3)
+    return np.stack([d, d + c / f32(3.0), (d + c * (f32(2.0) / f32(3.0))) + b / f32(3.0), ((a + b) + c) + d]).astype(np.float32)
+
+
+def _cubic_curve_spans(prim):
+    """curve_segments (usd_import.rs:1993-2131) for type = "cubic": [n, 14] float32 rows cp0 cp1 cp2 cp3 r0 r1, one per
+    span — span k of a curve uses its control points [k * vstep, k * vstep + 3] (bezier: vstep 3; bspline, catmullRom:
+    vstep 1), converted to Bezier form; (cnt - 4) // vstep + 1 spans per curve, curves of fewer than four points skipped.
+    The radii are those of the span's first and fourth control point, widths resolved as for linear curves. None when
+    points / curveVertexCounts are missing, the basis is not one USD knows, or no span results."""
+    pts, counts = prim.attr("points"), prim.attr("curveVertexCounts")
+    if pts is None or counts is None:
+        return None
+    basis = _CUBIC_BASES.get(prim.attr("basis", "bezier"))
+    if basis is None:
+        return None
+    m, vstep = basis
+    pts = np.asarray(pts, dtype=np.float32).reshape(-1, 3)
+    counts = [int(c) for c in np.asarray(counts).reshape(-1)]
+    widths = prim.attr("widths")
+    widths = np.asarray([1.0] if widths is None else widths, dtype=np.float32).reshape(-1)
+    if widths.size == 0:
+        widths = np.ones(1, dtype=np.float32)
+
+    def radius(point, curve):
+        w = widths[point] if widths.size == len(pts) else (widths[curve] if widths.size == len(counts) else widths[0])
+        return f32(0.5) * max(f32(w), f32(1e-6))
+
+    rows, offset = [], 0
+    with np.errstate(all="ignore"):
+        for ci, cnt in enumerate(counts):
+            if cnt < 0 or offset + cnt > len(pts):
+                break
+            if cnt >= 4:
+                for k in range((cnt - 4) // vstep + 1):
+                    base = offset + k * vstep
+                    rows.append([*_basis_to_bezier(m, pts[base:base + 4]).reshape(-1), radius(base, ci), radius(base + 3, ci)])
+            offset += cnt
+    if not rows:
+        return None
+    return np.asarray(rows, dtype=np.float32).reshape(-1, 14)
+
+
 def _camera(prim, world, settings):  # build_camera, usd_import.rs:2174-2220
     lookfrom = _xf_point(world, [(0.0, 0.0, 0.0)])[0]
     forward = _normalize(_xf_vec(world, (0.0, 0.0, -1.0)))
@@ -944,8 +1018,11 @@ def build_world(desc, api, new_material):
     protos = []
     for p in desc.protos:  # MeshArena::committed_scene, usd_import.rs:891-909; local sphere parts :1462-1484
         b = api.SceneBuilder()
-        if "segments" in p:  # a linear BasisCurves prim's segments, in its local space
-            b.attach_round_curves(p["segments"])
+        if "segments" in p or "spans" in p:  # a BasisCurves prim's segments / spans, in its local space (round first)
+            if "segments" in p:
+                b.attach_round_curves(p["segments"])
+            if "spans" in p:
+                b.attach_cubic_curves(p["spans"])
         elif "radius" in p:
             b.attach_sphere(p.get("center", (0.0, 0.0, 0.0)), float(p["radius"]))
         elif "instances" in p:  # a nested instancer's sub-scene: earlier protos placed once per nested instance
@@ -965,6 +1042,8 @@ def build_world(desc, api, new_material):
             b.attach_instance(protos[g["proto"]], g["l2w"], g.get("l2w_end"), mask=g["mask"])
         elif g["kind"] == "curves":  # round curve segments at the top level (hand-built descriptions; the reader instances them)
             b.attach_round_curves(g["segments"], mask=g["mask"])
+        elif g["kind"] == "cubic_curves":  # cubic spans at the top level (hand-built descriptions)
+            b.attach_cubic_curves(g["spans"], mask=g["mask"])
         else:
             b.attach_empty(mask=g["mask"])
         materials.append(fill_material(new_material(), g["material"]))

@@ -43,7 +43,7 @@ typedef enum {
                             * words of every instance level together) than its one device stack holds, 255 in the
                             * shipped build. The reference's stack has no limit; deep trees of overlapping boxes and
                             * nested instances can reach it */
-  CRT_ERR_UNSUPPORTED = -5, /* CubicCurves (scene.rs:103-106): out of scope */
+  CRT_ERR_UNSUPPORTED = -5, /* an engine instance asked for that cannot run the scene's image (crt_scene_engine_select) */
   CRT_ERR_NO_MEMORY = -6    /* a host allocation failed (the reference aborts); reason in crt_last_error. Nothing unwinds
                              * through this ABI: a C or Rust host could not catch it */
 } CrtStatus;
@@ -102,6 +102,12 @@ typedef struct CrtCurveSegment { float p0[3]; float r0; float p1[3]; float r1; }
 /* attach_masked(Geometry::RoundCurves{segments}, mask); prim_id of a hit = index of the segment   scene.rs:99-102, :277-289.
  * The array is copied. A NaN or an infinity in it is refused with CRT_ERR_BAD_ARG (reason in crt_last_error). */
 int crt_attach_round_curves(CrtBuilder *b, const CrtCurveSegment *segments, size_t n, uint32_t mask, uint32_t *geom_id_out);
+/* scene.rs:70-80 CubicCurveSegment: Bezier control points and the radii at the two ends. 56 bytes. */
+typedef struct CrtCubicCurveSegment { float cp[4][3]; float r0; float r1; } CrtCubicCurveSegment;
+/* attach_masked(Geometry::CubicCurves{segments}, mask); prim_id of a hit = index of the span       scene.rs:103-106, :290-301.
+ * The array is copied. A NaN or an infinity in it is refused with CRT_ERR_BAD_ARG (reason in crt_last_error). The span's
+ * subdivision depth (curve.rs:122-141) is derived once, at commit. */
+int crt_attach_cubic_curves(CrtBuilder *b, const CrtCubicCurveSegment *spans, size_t n, uint32_t mask, uint32_t *geom_id_out);
 /* attach_masked(Geometry::Instance{scene, transform, transform_end}, mask)            scene.rs:111-121.
  * l2w / l2w_end: glam Affine3A as 12 floats (matrix3 columns x, y, z then translation); l2w_end may be
  * NULL. The builder retains `scene`. */
@@ -114,6 +120,7 @@ int crt_set_triangles(CrtBuilder *b, uint32_t id, const float *verts, size_t n_v
                       size_t n_tris, const float *normals, size_t n_normals);
 int crt_set_sphere(CrtBuilder *b, uint32_t id, const float center[3], float radius);
 int crt_set_round_curves(CrtBuilder *b, uint32_t id, const CrtCurveSegment *segments, size_t n);
+int crt_set_cubic_curves(CrtBuilder *b, uint32_t id, const CrtCubicCurveSegment *spans, size_t n);
 int crt_set_instance(CrtBuilder *b, uint32_t id, CrtScene *scene, const float l2w[12], const float *l2w_end);
 /* commit(self) -> Scene: consumes the builder (scene.rs:226). Deterministic SBVH build + BVH4 collapse
  * on the host (bvh.rs:300-327) on a bounded number of helper threads; the device image is created on first query.
