@@ -116,7 +116,7 @@ class CrtMaterial(C.Structure):
 
 
 MAT_OPENPBR, MAT_EMISSIVE = 0, 1
-LIGHT_SPHERE, LIGHT_RECT, LIGHT_DISTANT, LIGHT_DOME = 0, 1, 2, 3
+LIGHT_SPHERE, LIGHT_RECT, LIGHT_DISTANT, LIGHT_DOME, LIGHT_DOME_MAP = 0, 1, 2, 3, 4
 STRATEGY = {"power": 0, "mis": 0, "balance": 1, "light": 2, "bsdf": 3}
 FILTER = {"box": 0, "triangle": 1}
 
@@ -125,6 +125,15 @@ class CrtLight(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("geom_id", C.c_uint32), ("radiance", C.c_float * 3),
                 ("center", C.c_float * 3), ("radius", C.c_float), ("origin", C.c_float * 3),
                 ("edge_u", C.c_float * 3), ("edge_v", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class CrtEnvironmentTables(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("id", C.c_uint32), ("marginal_integral", C.c_float),
+                ("marginal_func", C.POINTER(C.c_float)), ("marginal_cdf", C.POINTER(C.c_float)),
+                ("conditional_func", C.POINTER(C.c_float)), ("conditional_cdf", C.POINTER(C.c_float)),
+                ("conditional_integral", C.POINTER(C.c_float)),
+                ("light_to_world", C.c_float * 9), ("world_to_light", C.c_float * 9),
+                ("image", C.c_void_p), ("image_bytes", C.c_size_t)]
 
 
 class CrtCamera(C.Structure):
@@ -167,6 +176,7 @@ ABI_SYMBOLS = [
     "crt_light_escaped_n",
     "crt_shard_padded_count", "crt_gather_plan_new", "crt_gather_plan_free", "crt_gather_plan_padded_count",
     "crt_gather_plan_assemble", "crt_renderer_set_lanes",
+    "crt_environment_new", "crt_environment_free", "crt_environment_tables", "crt_light_dome_mapped",
 ]
 
 _lib = None
@@ -279,6 +289,13 @@ def lib():
                  "crt_light_pdf_n", "crt_light_escaped_n"):  # the shading seam (shading.py)
         if hasattr(L, name):
             getattr(L, name).argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "crt_environment_new"):
+        L.crt_environment_new.restype = vp
+        L.crt_environment_new.argtypes = [C.c_uint32, C.c_uint32, fp, fp]
+        L.crt_environment_free.restype = None
+        L.crt_environment_free.argtypes = [vp]
+        L.crt_environment_tables.argtypes = [vp, C.POINTER(CrtEnvironmentTables)]
+        L.crt_light_dome_mapped.argtypes = [C.POINTER(CrtLight), fp, vp]
     _lib = L
     return L
 
@@ -657,10 +674,73 @@ def make_camera(lookfrom, lookat, vup, vfov_deg, aspect, aperture, focus_dist):
     return c
 
 
+class Environment:
+    """EnvironmentMap + its dome's orientation (environment.rs:106-215, light.rs:320-337) over crt_environment_new.
+    rgb: [height, width, 3] (or flat) float32 HOST pixels, row 0 at +Y. light_to_world: 3x3 (its COLUMNS are the images
+    of the dome's axes) or None for identity. Building touches no device. The handle is ref-counted by the library: a
+    Renderer and a shading.DeviceLights keep the objects their lights name alive."""
+
+    def __init__(self, width, height, rgb, light_to_world=None):
+        px = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1) if rgb is not None else None
+        if px is not None and px.size != int(width) * int(height) * 3:
+            raise ValueError("Environment: %d floats for a %d x %d map" % (px.size, width, height))
+        m = None
+        if light_to_world is not None:
+            a = np.asarray(light_to_world, dtype=np.float32).reshape(3, 3)
+            m = np.ascontiguousarray(np.concatenate([a[:, 0], a[:, 1], a[:, 2]]), dtype=np.float32)
+        self.h = lib().crt_environment_new(int(width), int(height), _fp(px), _fp(m))
+        if not self.h:
+            raise CrtError(-1, "crt_environment_new")
+        self.width, self.height = int(width), int(height)
+
+    def free(self):
+        """Drops this object's reference now (crt_environment_free); the object is unusable afterwards."""
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            lib().crt_environment_free(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def tables(self):
+        """What EnvironmentMap::new built, as numpy copies (crt_environment_tables)."""
+        t = CrtEnvironmentTables()
+        _check(lib().crt_environment_tables(self.h, C.byref(t)), "crt_environment_tables")
+        w, h = int(t.width), int(t.height)
+        arr = lambda p, *shape: np.ctypeslib.as_array(p, shape=shape).copy()
+        return dict(width=w, height=h, id=int(t.id), marginal_integral=np.float32(t.marginal_integral),
+                    marginal_func=arr(t.marginal_func, h), marginal_cdf=arr(t.marginal_cdf, h + 1),
+                    conditional_func=arr(t.conditional_func, h, w), conditional_cdf=arr(t.conditional_cdf, h, w + 1),
+                    conditional_integral=arr(t.conditional_integral, h),
+                    light_to_world=np.array(t.light_to_world, dtype=np.float32).reshape(3, 3).T.copy(),
+                    world_to_light=np.array(t.world_to_light, dtype=np.float32).reshape(3, 3).T.copy(),
+                    image=np.ctypeslib.as_array(C.cast(t.image, C.POINTER(C.c_uint8)), shape=(int(t.image_bytes),)).copy())
+
+
+def environment_of(d):
+    """The Environment a light dict names: an Environment object, or the pixels-and-rotation dict a SceneDesc carries
+    (usda.dome_light: width, height, rgb, light_to_world) — built here, never stored on the dict, so that the
+    description stays plain data that survives shard.import_once's broadcast."""
+    env = d.get("environment")
+    if env is None or isinstance(env, Environment):
+        return env
+    return Environment(env["width"], env["height"], env["rgb"], env.get("light_to_world"))
+
+
 def make_lights(light_dicts):
     arr = (CrtLight * max(len(light_dicts), 1))()
+    keep = []
     for k, d in enumerate(light_dicts):
         l = arr[k]
+        if d["kind"] == "dome" and d.get("environment") is not None:  # DomeLight with a map (crt_light_dome_mapped)
+            env = environment_of(d)
+            tint = np.asarray(d["radiance"], dtype=np.float32)
+            _check(lib().crt_light_dome_mapped(C.byref(l), _fp(tint), env.h), "crt_light_dome_mapped")
+            keep.append(env)
+            continue
         l.kind = {"sphere": LIGHT_SPHERE, "rect": LIGHT_RECT, "distant": LIGHT_DISTANT,
                   "dome": LIGHT_DOME}[d["kind"]]
         l.geom_id = int(d["geom_id"])
@@ -677,6 +757,7 @@ def make_lights(light_dicts):
         else:
             for f in ("origin", "edge_u", "edge_v", "normal"):
                 getattr(l, f)[:] = [float(x) for x in d[f]]
+    arr._environments = keep  # the array keeps the environments its records name alive
     return arr
 
 
@@ -814,14 +895,16 @@ def scene_path(name):
 
 
 def load_usda(path, width=None, height=None, max_depth=None, rank=0, world=1, variance=0.0, min_spp=None, dist=None,
-              timings=None, cubic_curves=False):
+              timings=None, cubic_curves=False, environment_maps=False):
     """Scene::from_usd (scene.rs / usd_import.rs:287-424) for the text sample scenes -> (Renderer, desc).
     `path` may also name a synthetic scene: "synthetic:city" or "synthetic:city:<side>" (synthetic.py).
     variance > 0 enables adaptive stopping (the scene files' own default is 0.05; 0 = every sample, the rule for
     comparable runs, scripts/check_images.sh:5-11). dist: the job's torch.distributed module — the file is then imported
     by rank 0 only and broadcast (shard.import_once). timings: a dict that receives `import_s` (this rank's share of the
     import: parsing on rank 0, waiting for the broadcast elsewhere) and `commit_s` (build_world: every rank's own commit).
-    cubic_curves: decode cubic BasisCurves prims into cubic spans (usda.load); off, they are warned about and skipped."""
+    cubic_curves: decode cubic BasisCurves prims into cubic spans (usda.load); off, they are warned about and skipped.
+    environment_maps: decode a DomeLight's lat-long EXR into an importance-sampled environment (usda.load); off, the dome
+    keeps its uniform colour."""
     from . import usda, shard
     import sys
     import time
@@ -832,7 +915,7 @@ def load_usda(path, width=None, height=None, max_depth=None, rank=0, world=1, va
         kw = dict(side=int(parts[2])) if len(parts) > 2 else {}
         desc = getattr(synthetic, parts[1])(width or 640, height or 360, **kw)
     else:
-        desc = shard.import_once(path, width, height, dist, cubic_curves=cubic_curves)
+        desc = shard.import_once(path, width, height, dist, cubic_curves=cubic_curves, environment_maps=environment_maps)
     me = sys.modules[__name__]
     t1 = time.perf_counter()
     scene, materials, protos = usda.build_world(desc, me, default_material)

@@ -430,6 +430,11 @@ int launch_intersect_n(const DevScene &s, const CrtRay *d_rays, size_t n, float 
 int launch_occluded_n(const DevScene &s, const CrtRay *d_rays, size_t n, float t_min, float t_max, uint32_t *d_out,
                       void *stream, CrtTravStats *d_stats, uint32_t *d_err);
 int device_ok();
+// Environment maps (environment.cpp). env_table_for_launch: the device table of live environments for a launch of the
+// library's own, every live one uploaded first; *table = nullptr when none is live. env_retain: a reference to the
+// environment with that id, or nothing when the id names none.
+int env_table_for_launch(const void **table);
+std::shared_ptr<void> env_retain(uint32_t id);
 // printf-style text for crt_last_error() on this thread (failures that are not HIP calls).
 void set_error_text(const char *fmt, ...);
 // Nothing may unwind through the C ABI — a host in C or Rust cannot catch it, and unwinding into its frames is undefined:

@@ -9,7 +9,7 @@
 // final rounding to f32 they are within 1 ulp, the same contract as the f32::sin/cos/acos/exp/ln/powf the
 // reference calls (brdf.rs:101-102, :270; light.rs:28-34; common.rs:128-135; openpbr.rs:598, :802).
 // That bound is measured, against float64 libm and 120-bit mpmath, by tests/test_math_host.py (DESIGN.md §2 has the
-// maxima) on these domains: sincos |x| <= 2^20*pi/2 (see sincos_det), acos [-1, 1], exp [-103.98, 88.73], log every
+// maxima) on these domains: sincos |x| <= 2^20*pi/2 (see sincos_det), acos [-1, 1], atan2 every pair (tests/test_environment.py), exp [-103.98, 88.73], log every
 // finite positive f32, pow every pair with a finite normal result. tests/test_gpu_math.py pins the device bits.
 // CDNA4 runs f64 FMA/ADD/MUL at half the f32 vector rate, so a sincos costs ~20 DP ops: cheap next to
 // the BVH traversal that dominates a path vertex.
@@ -57,7 +57,8 @@ __device__ __forceinline__ float max_elem(V3 a) { return smax(smax(a.x, a.y), a.
 __device__ __forceinline__ float comp(V3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
 
 // ---- sin / cos ----
-__device__ __forceinline__ double ksin(double x) {
+// (__host__ too: the environment map's row weights are built on the host from this very sincos_det, environment.cpp)
+__host__ __device__ __forceinline__ double ksin(double x) {
   const double S1 = -0.166666666416265235595, S2 = 0.0083333293858894631756, S3 = -0.000198393348360966317347,
                S4 = 0.0000027183114939898219064;
   const double z = x * x;
@@ -66,7 +67,7 @@ __device__ __forceinline__ double ksin(double x) {
   const double s = z * x;
   return (x + s * (S1 + z * S2)) + s * w * r;
 }
-__device__ __forceinline__ double kcos(double x) {
+__host__ __device__ __forceinline__ double kcos(double x) {
   const double C0 = -0.499999997251031003120, C1 = 0.0416666233237390631894, C2 = -0.00138867637746099294692,
                C3 = 0.0000243904487962774090654;
   const double z = x * x;
@@ -81,7 +82,7 @@ __device__ __forceinline__ double kcos(double x) {
 // large is a multiple of 2^39, its phase is not information. The guard also keeps the double -> integer conversion
 // of fn in range: out of range it is undefined in C, x86 and gfx950 answer differently (INT64_MIN vs saturation),
 // and an authored thin_film_thickness reaches it (thin_film_lambda). Bits for |x| < 2^62 are those of the unguarded form.
-__device__ __forceinline__ void sincos_det(float xf, float &s, float &c) {
+__host__ __device__ __forceinline__ void sincos_det(float xf, float &s, float &c) {
   const double INV_PIO2 = 6.36619772367581382433e-01;
   const double PIO2_HI = 1.57079632673412561417e+00;
   const double PIO2_LO = 6.07710050650619224932e-11;
@@ -126,6 +127,61 @@ __device__ __forceinline__ float acos_det(float xf) {
   const double s = sqrt(z);
   const double t = 2.0 * (s + s * asin_r(z));
   return (float)(x < 0.0 ? PI_D - t : t);
+}
+
+// ---- atan2 ----
+// msun's s_atan.c on |y / x| in double: the four-interval reduction (breakpoints 7/16, 11/16, 19/16, 39/16 around
+// atan(0.5), atan(1), atan(1.5), atan(inf)) and the degree-11 odd polynomial in its even/odd split.
+__device__ __forceinline__ double atan_pos_d(double x) {  // x >= 0, finite
+  const double HI0 = 4.63647609000806093515e-01, HI1 = 7.85398163397448278999e-01, HI2 = 9.82793723247329054082e-01,
+               HI3 = 1.57079632679489655800e+00;
+  const double LO0 = 2.26987774529616870924e-17, LO1 = 3.06161699786838301793e-17, LO2 = 1.39033110312309984516e-17,
+               LO3 = 6.12323399573676603587e-17;
+  const double T0 = 3.33333333333329318027e-01, T1 = -1.99999999998764832476e-01, T2 = 1.42857142725034663711e-01,
+               T3 = -1.11111104054623557880e-01, T4 = 9.09088713343650656196e-02, T5 = -7.69187620504482999495e-02,
+               T6 = 6.66107313738753120669e-02, T7 = -5.83357013379057348645e-02, T8 = 4.97687799461593236017e-02,
+               T9 = -3.65315727442169155270e-02, T10 = 1.62858201153657823623e-02;
+  if (x >= 73786976294838206464.0) return HI3 + LO3;  // 2^66
+  double hi = 0.0, lo = 0.0;
+  bool reduced = true;
+  if (x < 0.4375) reduced = false;
+  else if (x < 0.6875) { hi = HI0; lo = LO0; x = (2.0 * x - 1.0) / (2.0 + x); }
+  else if (x < 1.1875) { hi = HI1; lo = LO1; x = (x - 1.0) / (x + 1.0); }
+  else if (x < 2.4375) { hi = HI2; lo = LO2; x = (x - 1.5) / (1.0 + 1.5 * x); }
+  else { hi = HI3; lo = LO3; x = -1.0 / x; }
+  const double z = x * x;
+  const double w = z * z;
+  const double s1 = z * (T0 + w * (T2 + w * (T4 + w * (T6 + w * (T8 + w * T10)))));
+  const double s2 = w * (T1 + w * (T3 + w * (T5 + w * (T7 + w * T9))));
+  if (!reduced) return x - x * (s1 + s2);
+  return hi - ((x * (s1 + s2) - lo) - x);
+}
+// f32::atan2(y, x) (environment.rs:158) with e_atan2.c's quadrant logic; every case is decided on the operands, the
+// double quotient |y / x| of two finite non-zero f32 neither overflows nor underflows. Special cases, in this order:
+//   a NaN operand                -> NaN
+//   y = +-0:  x > 0 or x = +0    -> +-0 (y itself);   x < 0 or x = -0 -> +-pi      (the u seam of the lat-long map)
+//   x = +-0 (y != 0)             -> +-pi/2
+//   x = +inf: y = +-inf -> +-pi/4, y finite -> +-0;   x = -inf: y = +-inf -> +-3pi/4, y finite -> +-pi
+//   y = +-inf (x finite)         -> +-pi/2
+// The sign is y's. pi is (float)PI_D, the f32 ABOVE pi, as f32::atan2 answers; a result below the smallest subnormal
+// rounds to a signed zero.
+__device__ __forceinline__ float atan2_det(float yf, float xf) {
+  const double PI_D = 3.14159265358979311600e+00, PI_LO = 1.2246467991473531772e-16, PIO2 = 1.57079632679489655800e+00;
+  const double PIO4 = 7.85398163397448278999e-01, PI3O4 = 2.35619449019234483700e+00;
+  if (yf != yf || xf != xf) return __uint_as_float(0x7fc00000u);
+  const bool yneg = (__float_as_uint(yf) >> 31) != 0, xneg = (__float_as_uint(xf) >> 31) != 0;
+  const double y = (double)fabs_(yf), x = (double)fabs_(xf);
+  const double inf = (double)CRT_INF;
+  double r;
+  if (y == 0.0) { if (!xneg) return yf; r = PI_D; }
+  else if (x == 0.0) r = PIO2;
+  else if (x == inf) r = y == inf ? (xneg ? PI3O4 : PIO4) : (xneg ? PI_D : 0.0);
+  else if (y == inf) r = PIO2;
+  else {
+    const double z = atan_pos_d(y / x);
+    r = xneg ? PI_D - (z - PI_LO) : z;
+  }
+  return (float)(yneg ? -r : r);
 }
 
 // ---- exp / log / pow ----

@@ -206,6 +206,9 @@ struct Params {
   // plane `a` — its origin is the camera's, its throughput 1, its radiance 0, pixel / sample / depth follow from the slot
   // number (generate_segment). Set per batch by Renderer::render.
   uint32_t cam_compact;
+  // The library's table of live environments (environment.cpp), read by the mapped-dome instances only (k_shade_env):
+  // a CRT_LIGHT_DOME_MAP record names its environment by id. nullptr when the light list holds no such record.
+  const EnvSlot *envs;
 };
 
 __device__ __forceinline__ float light_weight(int s, float light_pdf, float bounce_pdf) {  // tracer.rs:85-92
@@ -230,14 +233,15 @@ __device__ __forceinline__ V3 sky_gradient(V3 unit_direction) {
   const float t = 0.5f * (unit_direction.y + 1.0f);
   return v3(1.0f, 1.0f, 1.0f) * (1.0f - t) + v3(0.5f, 0.7f, 1.0f) * t;
 }
+template <bool ENV = false>
 __device__ __forceinline__ V3 escaped_background(const CrtLight *lights, uint32_t n_lights, int strategy,
-                                                 V3 unit_direction, bool competing, float prev_pdf) {
+                                                 V3 unit_direction, bool competing, float prev_pdf, const EnvSlot *envs = nullptr) {
   V3 background = splat(0.0f);
   bool covered = false;
   for (uint32_t k = 0; k < n_lights; k++) {
     V3 emitted;
     float pdf;
-    if (!light_escaped(lights[k], unit_direction, emitted, pdf)) continue;
+    if (!light_escaped_env<ENV>(lights[k], envs, unit_direction, emitted, pdf)) continue;
     covered = true;
     float weight = 1.0f;
     if (competing && strategy != CRT_STRATEGY_BSDF) {
@@ -554,7 +558,8 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend(
 #ifndef CRT_SHADE_STAMPS
 #define CRT_SHADE_STAMPS 0
 #endif
-template <int MATS, bool INF, bool LIT, int ARENA, bool DRV>
+// INF: 0 no light at infinity in the list | 1 distant lights and uniform domes | 2 mapped domes too (k_shade_env)
+template <int MATS, int INF, bool LIT, int ARENA, bool DRV>
 __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                               const ShadowSoA &Q, Counters *C, int cur, float4 *staging,
                                               uint32_t *sobol_tab /* ARENA dwords: Sobol tables, then the material table */,
@@ -870,7 +875,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
           const bool competing = prev_valid && !prev_delta;
           float prev_pdf = 0.0f;
           if (INF && competing) prev_pdf = S.e[i].w;
-          const V3 background = INF ? escaped_background(P.lights, n_lights, P.strategy, unit_direction, competing, prev_pdf)
+          const V3 background = INF ? escaped_background<INF == 2>(P.lights, n_lights, P.strategy, unit_direction, competing, prev_pdf, P.envs)
                                     : splat(0.0f) + sky_gradient(unit_direction);
           L = L + beta * background;
         } else {
@@ -897,7 +902,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
             if (li > n_lights - 1) li = n_lights - 1;
             const CrtLight &light = P.lights[li];
             LightSample ls;
-            if (light_sample_li<INF>(light, rec.p, nee_s[1], nee_s[2], ls)) {
+            if (light_sample_li_env<INF>(light, P.envs, rec.p, nee_s[1], nee_s[2], ls)) {
               s_shadow++;  // the reference traces the shadow ray before it evaluates the BSDF (tracer.rs:1412-1425)
               want_shadow = true;
               sh_d = ls.direction;
@@ -1007,7 +1012,16 @@ __global__ __launch_bounds__(kBlock, WIDE ? CRT_SHADE_WIDE_WAVES : CRT_SHADE_WAV
   static_assert(LIT || !INF, "lights at infinity are lights");
   constexpr int ARENA = WIDE ? kArenaWide : kArenaDwords;
   __shared__ uint32_t sobol_tab[ARENA];
-  shade_segment<MATS, INF, LIT, ARENA, DRV>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
+  shade_segment<MATS, INF ? 1 : 0, LIT, ARENA, DRV>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
+}
+// The instances of light lists that hold a mapped dome (CRT_LIGHT_DOME_MAP): k_shade<MATS, true, false, true, DRV> with
+// the environment arm of light_sample_li_env / light_escaped_env compiled in. Kernels of their own, so that every other
+// scene runs exactly the code it ran before mapped domes existed.
+template <int MATS, bool DRV>
+__global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_env(Params P, PathSoA S, PathSoA N, HitSoA H, ShadowSoA Q,
+                                                                       Counters *C, int cur, float4 *staging, int first) {
+  __shared__ uint32_t sobol_tab[kArenaDwords];
+  shade_segment<MATS, 2, true, kArenaDwords, DRV>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
 }
 
 // ---- shade, PIPELINED: the four-wave kernel of unlit simple-material scenes with one material class (cornellbox, the
@@ -1564,6 +1578,7 @@ struct Renderer {
   bool fused = true;       // what the LAST batch ran (crt_renderer_pipeline)
   int cus = 256, fused_mult = 3, stage_mult = 8, mult_forced = 0;
   CrtLight *d_lights = nullptr;
+  std::vector<std::shared_ptr<void>> environments;  // what the mapped domes of the light list name (Params::envs is set iff any)
   uint32_t *d_pixels = nullptr;
   int grid = 768;          // of the last batch; the film kernels use it too
   hipStream_t last_stream = nullptr;
@@ -1908,7 +1923,15 @@ struct Renderer {
   timed(1, st, [&] { hipLaunchKernelGGL((k_shade<M, I, W, L, D>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (it == 0 ? 1 : 0) | ((int)it >= noclassify_from ? 2 : 0)); })
       // the instance: material table (MATS), lights at infinity (INF), four waves (simple materials without lights at
       // infinity, when the scene runs the wide kernels), and — as for k_path — whether the light list is empty
-      if (mats_kind == 2) { if (P.has_inf_lights) CRT_SHADE(2, true, false, true); else if (lit) CRT_SHADE(2, false, false, true); else CRT_SHADE(2, false, false, false); }
+#define CRT_SHADE_ENV(M, D) \
+  timed(1, st, [&] { hipLaunchKernelGGL((k_shade_env<M, D>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (it == 0 ? 1 : 0) | ((int)it >= noclassify_from ? 2 : 0)); })
+      if (P.envs) {  // the light list holds a mapped dome: the instances with the environment arm
+        if (mats_kind == 2) CRT_SHADE_ENV(2, false);
+        else if (mats_kind == 1) CRT_SHADE_ENV(1, false);
+        else if (drv) CRT_SHADE_ENV(0, true);
+        else CRT_SHADE_ENV(0, false);
+      }
+      else if (mats_kind == 2) { if (P.has_inf_lights) CRT_SHADE(2, true, false, true); else if (lit) CRT_SHADE(2, false, false, true); else CRT_SHADE(2, false, false, false); }
       else if (mats_kind == 1) { if (P.has_inf_lights) CRT_SHADE(1, true, false, true); else if (lit) CRT_SHADE(1, false, false, true); else CRT_SHADE(1, false, false, false); }
       else if (P.has_inf_lights) CRT_SHADE0(true, false, true);
       else if (wide && !P.mat_index && shade_wide != 0) {
@@ -1923,6 +1946,7 @@ struct Renderer {
         else CRT_SHADE0(false, true, false);
       }
       else { if (lit) CRT_SHADE0(false, false, true); else CRT_SHADE0(false, false, false); }
+#undef CRT_SHADE_ENV
 #undef CRT_SHADE_D
 #undef CRT_SHADE0
 #undef CRT_SHADE
@@ -2011,8 +2035,21 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   P.n_materials = (uint32_t)n_materials;
   P.has_inf_lights = 0;
   for (size_t k = 0; k < n_lights; k++) {
-    if (lights[k].kind > CRT_LIGHT_DOME) return nullptr;
+    if (lights[k].kind > CRT_LIGHT_DOME_MAP) { set_error_text("crt_renderer_new: light %zu has the unknown kind %u", k, lights[k].kind); return nullptr; }
     if (lights[k].kind >= CRT_LIGHT_DISTANT) P.has_inf_lights = 1;
+    if (lights[k].kind == CRT_LIGHT_DOME_MAP) {  // retained like the scene; an id that names no live environment is refused
+      uint32_t id;
+      std::memcpy(&id, &lights[k].center[0], 4);
+      std::shared_ptr<void> env = env_retain(id);
+      if (!env) { set_error_text("crt_renderer_new: light %zu names environment id 0x%x, which is not live", k, id); return nullptr; }
+      r.environments.push_back(std::move(env));
+    }
+  }
+  P.envs = nullptr;
+  if (!r.environments.empty()) {
+    const void *table = nullptr;
+    if (env_table_for_launch(&table) != CRT_OK || !table) return nullptr;
+    P.envs = static_cast<const EnvSlot *>(table);
   }
   P.camera = *camera;
   P.width = settings->width; P.height = settings->height; P.max_depth = settings->max_depth;

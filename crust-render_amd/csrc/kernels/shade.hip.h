@@ -8,6 +8,7 @@
 #pragma once
 
 #include "dmath.hip.h"
+#include "envmap.hip.h"
 #include "qmc.hip.h"
 #include "../../../include/crt.h"
 
@@ -826,6 +827,30 @@ __device__ __forceinline__ bool light_sample_li(const CrtLight &l, V3 from, floa
   out.radiance = ld3(l.radiance);
   out.pdf = solid_angle_pdf(l, from, lp);
   return true;
+}
+// The two functions above with the mapped dome's arm (DomeLight with an EnvironmentMap, light.rs:340-388; envmap.hip.h).
+// ENV / INF == 2: compiled only into the kernel instances of their own that light lists holding a CRT_LIGHT_DOME_MAP
+// record run; every other instance calls straight through. A record whose id names no live environment answers None.
+template <bool ENV>
+__device__ __forceinline__ bool light_escaped_env(const CrtLight &l, const EnvSlot *envs, V3 direction, V3 &radiance, float &pdf) {
+  if (ENV && l.kind == CRT_LIGHT_DOME_MAP) {
+    const EnvHeader *E = env_lookup(envs, __float_as_uint(l.center[0]));
+    if (!E) return false;
+    env_light_escaped(E, ld3(l.radiance), direction, radiance, pdf);
+    return true;
+  }
+  return light_escaped(l, direction, radiance, pdf);
+}
+template <int INF>
+__device__ __forceinline__ bool light_sample_li_env(const CrtLight &l, const EnvSlot *envs, V3 from, float u, float v, LightSample &out) {
+  if (INF == 2 && l.kind == CRT_LIGHT_DOME_MAP) {
+    const EnvHeader *E = env_lookup(envs, __float_as_uint(l.center[0]));
+    if (!E) return false;
+    if (!env_light_sample(E, ld3(l.radiance), u, v, out.direction, out.radiance, out.pdf)) return false;
+    out.distance = CRT_INF;
+    return true;
+  }
+  return light_sample_li<INF != 0>(l, from, u, v, out);
 }
 
 // ---- camera.rs:71-84 ----

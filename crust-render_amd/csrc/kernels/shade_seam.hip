@@ -109,17 +109,19 @@ __device__ __forceinline__ void store_lsample(CrtLightSample *out, bool some, V3
 }
 
 // mode 0: Light::sample_li (light.rs:126) | 1: Light::pdf_at_point (:132) | 2: Light::escaped (:141)
-template <int MODE>
+// ENV: the instance with the mapped dome's arm, launched while the library holds a live environment (envs = its table);
+// without one no CRT_LIGHT_DOME_MAP record can name anything, and the other instance answers None for that kind.
+template <int MODE, bool ENV>
 __global__ __launch_bounds__(kSeamBlock) void k_seam_light(const CrtLight *lights, uint32_t n_lights, const CrtLightQuery *qs, size_t n,
-                                                           CrtLightSample *out, float *pdf_out) {
+                                                           CrtLightSample *out, float *pdf_out, const EnvSlot *envs) {
   const size_t i = (size_t)blockIdx.x * kSeamBlock + threadIdx.x;
   if (i >= n) return;
   const LQuery q = load_lquery(qs + i);
-  const bool ok = q.light < n_lights;
+  const bool ok = q.light < n_lights && lights[q.light].kind <= (uint32_t)(ENV ? CRT_LIGHT_DOME_MAP : CRT_LIGHT_DOME);
   if (MODE == 0) {
     LightSample ls;
     ls.direction = ls.radiance = splat(0.0f); ls.distance = 0.0f; ls.pdf = 0.0f;
-    const bool some = ok && light_sample_li<true>(lights[q.light], q.from, q.u, q.v, ls);
+    const bool some = ok && light_sample_li_env<ENV ? 2 : 1>(lights[q.light], envs, q.from, q.u, q.v, ls);
     store_lsample(out + i, some, ls.direction, ls.distance, ls.radiance, ls.pdf);
   } else if (MODE == 1) {
     float pdf = 0.0f;  // the trait's default for lights at infinity (light.rs:132-134)
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(kSeamBlock) void k_seam_light(const CrtLight *light
   } else {
     V3 rad = splat(0.0f);
     float pdf = 0.0f;
-    const bool some = ok && light_escaped(lights[q.light], q.point, rad, pdf);
+    const bool some = ok && light_escaped_env<ENV>(lights[q.light], envs, q.point, rad, pdf);
     store_lsample(out + i, some, q.point, CRT_INF, rad, pdf);
   }
 }
@@ -141,6 +143,20 @@ int seam_args(const void *table, size_t n_table, const void *queries, size_t n, 
 }
 unsigned seam_grid(size_t n) { return (unsigned)((n + kSeamBlock - 1) / kSeamBlock); }
 int seam_done() { return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : CRT_ERR_NO_DEVICE; }
+template <int MODE>
+int seam_light(const CrtLight *d_lights, size_t n_lights, const CrtLightQuery *d_queries, size_t n, CrtLightSample *d_out,
+               float *d_pdf, void *stream) {
+  const void *table = nullptr;
+  const int rc = env_table_for_launch(&table);
+  if (rc != CRT_OK) return rc;
+  if (table)
+    hipLaunchKernelGGL((k_seam_light<MODE, true>), dim3(seam_grid(n)), dim3(kSeamBlock), 0, (hipStream_t)stream, d_lights,
+                       (uint32_t)n_lights, d_queries, n, d_out, d_pdf, static_cast<const EnvSlot *>(table));
+  else
+    hipLaunchKernelGGL((k_seam_light<MODE, false>), dim3(seam_grid(n)), dim3(kSeamBlock), 0, (hipStream_t)stream, d_lights,
+                       (uint32_t)n_lights, d_queries, n, d_out, d_pdf, (const EnvSlot *)nullptr);
+  return seam_done();
+}
 
 }  // namespace
 }  // namespace crt
@@ -177,25 +193,19 @@ int crt_light_sample_n(const CrtLight *d_lights, size_t n_lights, const CrtLight
                        CrtLightSample *d_out, void *stream) {
   const int rc = seam_args(d_lights, n_lights, d_queries, n, d_out);
   if (rc != CRT_OK) return rc > 0 ? CRT_OK : rc;
-  hipLaunchKernelGGL((k_seam_light<0>), dim3(seam_grid(n)), dim3(kSeamBlock), 0, (hipStream_t)stream, d_lights, (uint32_t)n_lights,
-                     d_queries, n, d_out, (float *)nullptr);
-  return seam_done();
+  return seam_light<0>(d_lights, n_lights, d_queries, n, d_out, nullptr, stream);
 }
 int crt_light_pdf_n(const CrtLight *d_lights, size_t n_lights, const CrtLightQuery *d_queries, size_t n, float *d_pdf,
                     void *stream) {
   const int rc = seam_args(d_lights, n_lights, d_queries, n, d_pdf);
   if (rc != CRT_OK) return rc > 0 ? CRT_OK : rc;
-  hipLaunchKernelGGL((k_seam_light<1>), dim3(seam_grid(n)), dim3(kSeamBlock), 0, (hipStream_t)stream, d_lights, (uint32_t)n_lights,
-                     d_queries, n, (CrtLightSample *)nullptr, d_pdf);
-  return seam_done();
+  return seam_light<1>(d_lights, n_lights, d_queries, n, nullptr, d_pdf, stream);
 }
 int crt_light_escaped_n(const CrtLight *d_lights, size_t n_lights, const CrtLightQuery *d_queries, size_t n,
                         CrtLightSample *d_out, void *stream) {
   const int rc = seam_args(d_lights, n_lights, d_queries, n, d_out);
   if (rc != CRT_OK) return rc > 0 ? CRT_OK : rc;
-  hipLaunchKernelGGL((k_seam_light<2>), dim3(seam_grid(n)), dim3(kSeamBlock), 0, (hipStream_t)stream, d_lights, (uint32_t)n_lights,
-                     d_queries, n, d_out, (float *)nullptr);
-  return seam_done();
+  return seam_light<2>(d_lights, n_lights, d_queries, n, d_out, nullptr, stream);
 }
 
 }  // extern "C"

@@ -78,6 +78,7 @@ class DeviceLights:
         crt = _crt()
         self.n = len(lights)
         arr = crt.make_lights(lights) if (self.n and isinstance(lights[0], dict)) else lights
+        self._environments = getattr(arr, "_environments", [])  # what mapped domes name stays alive with the table
         self.d = to_device(arr, device)
 
     def sample_li(self, d_queries, stream=None):  # light.rs:126 -> LIGHT_SAMPLE records

@@ -90,7 +90,7 @@ def gather_frame(film_local, width, height, rank, world, dist=None):
     return GatherPlan(width, height, world, film_local.device).gather(film_local, dist)
 
 
-def import_once(path, width=None, height=None, dist=None, src=0, cubic_curves=False):
+def import_once(path, width=None, height=None, dist=None, src=0, cubic_curves=False, environment_maps=False):
     """The scene description of a multi-rank job, imported ONCE: rank `src` reads and composes the USD file
     (usda.load: seconds for PointInstancedMedCity's crate, 14 s for the packed stress scene's 15.6 MB of text), every
     other rank receives the result in one object broadcast instead of parsing the file again on its own cores.
@@ -98,8 +98,10 @@ def import_once(path, width=None, height=None, dist=None, src=0, cubic_curves=Fa
     tree. Without a process group (dist None or world 1) this is usda.load."""
     from . import usda
     if dist is None or dist.get_world_size() == 1:
-        return usda.load(path, width, height, cubic_curves=cubic_curves)
-    box = [usda.load(path, width, height, cubic_curves=cubic_curves) if dist.get_rank() == src else None]
+        return usda.load(path, width, height, cubic_curves=cubic_curves, environment_maps=environment_maps)
+    # (a decoded environment travels as pixels and a rotation, never as a handle: usda.dome_light)
+    box = [usda.load(path, width, height, cubic_curves=cubic_curves, environment_maps=environment_maps)
+           if dist.get_rank() == src else None]
     dist.broadcast_object_list(box, src=src)
     return box[0]
 

@@ -478,16 +478,65 @@ def distant_light(direction, irradiance, angle_deg=0.53):
                 cos_half_angle=cos_half, solid_angle=omega)
 
 
-def dome_light(tint):
-    """DomeLight without an environment map (light.rs:320-390): a uniform sky of radiance `tint`."""
-    return dict(kind="dome", geom_id=0xFFFFFFFF, radiance=np.asarray(tint, dtype=np.float32))
+def dome_light(tint, environment=None):
+    """DomeLight (light.rs:320-390): a uniform sky of radiance `tint`, or — with `environment` — `tint` times a lat-long
+    map. environment: an Environment object of the package, or plain data dict(width, height, rgb [h, w, 3] float32 with
+    row 0 at +Y, light_to_world 3x3 or None), which is what a SceneDesc carries so that it pickles."""
+    d = dict(kind="dome", geom_id=0xFFFFFFFF, radiance=np.asarray(tint, dtype=np.float32))
+    if environment is not None:
+        d["environment"] = environment
+    return d
 
 
-def load(path, width=None, height=None, cubic_curves=False):
+def _normalize_or(v, fallback):
+    """glam Vec3A::normalize_or: v * (1 / length) when that reciprocal is finite and positive, else the fallback."""
+    f32 = np.float32
+    v = np.asarray(v, dtype=np.float32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        rcp = f32(1.0) / np.sqrt(f32(f32(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+    if np.isfinite(rcp) and rcp > 0:
+        return (v * rcp).astype(np.float32)
+    return np.asarray(fallback, dtype=np.float32)
+
+
+def _dome_environment(prim, world, layer_dir):
+    """The environment of a DomeLight prim as plain data, or None with a warning (usd_import.rs:2402-2448): the texture
+    path is resolved against the layer's directory, only lat-long EXR images are decoded, and the rotation is the world
+    transform's three axes, each normalised (translation and scale mean nothing at infinity)."""
+    import os
+    import warnings
+    from . import exr
+    tex = prim.attr("inputs:texture:file", None)
+    if tex is None:
+        return None
+    fmt = prim.attr("inputs:texture:format", None)
+    if fmt not in (None, "latlong", "automatic"):
+        warnings.warn(f"DomeLight {prim.name}: texture:format \"{fmt}\" is not supported (only latlong), using the uniform colour")
+        return None
+    path_ = str(tex).strip("@")
+    if not os.path.isabs(path_):
+        path_ = os.path.join(layer_dir, path_)
+    rgb = None
+    if path_.lower().endswith(".exr"):
+        try:
+            rgb = np.ascontiguousarray(exr.read_exr(path_), dtype=np.float32)
+        except Exception:
+            rgb = None
+    if rgb is None or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] == 0 or rgb.shape[1] == 0:
+        warnings.warn(f"DomeLight {prim.name}: could not load {path_}, using the uniform colour")
+        return None
+    axes = [_normalize_or(world[0:3, c], fb) for c, fb in enumerate(((1, 0, 0), (0, 1, 0), (0, 0, 1)))]
+    return dict(width=int(rgb.shape[1]), height=int(rgb.shape[0]), rgb=rgb,
+                light_to_world=np.stack(axes, axis=1).astype(np.float32))
+
+
+def load(path, width=None, height=None, cubic_curves=False, environment_maps=False):
     """Reads a .usda file into a SceneDesc. width/height override the RenderSettings resolution BEFORE the
     camera is built (the aspect ratio feeds Camera::new; the reference can only do this by editing the USD).
     cubic_curves: decode cubic BasisCurves prims into cubic spans (Geometry::CubicCurves) as the reference's importer
-    does; by default they are named in a warning and skipped, as before the backend could trace them."""
+    does; by default they are named in a warning and skipped, as before the backend could trace them.
+    environment_maps: decode a DomeLight's inputs:texture:file (a lat-long EXR beside the layer) into an environment the
+    dome importance-samples (usd_import.rs:2389-2460); by default the dome keeps its uniform colour, with a warning."""
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:6] == b"\xfd7zXZ\x00":  # an .xz-compressed stage (scenes/stress.usda.xz: 15 MB of generated text, 0.7 MB packed)
@@ -818,12 +867,16 @@ def load(path, width=None, height=None, cubic_curves=False):
             if light is not None:
                 desc.lights.append(light)
         elif t == "DomeLight":  # usd_import.rs:2389-2460
-            if prim.attr("inputs:texture:file", None) is not None:
+            env = None
+            if environment_maps:
+                import os
+                env = _dome_environment(prim, world, os.path.dirname(os.path.abspath(path)))
+            elif prim.attr("inputs:texture:file", None) is not None:
                 # No AssetLoader stands behind this importer: as when the reference's host declines to decode the
                 # image (usd_import.rs:2419-2426), the dome falls back to its uniform colour.
                 import warnings
                 warnings.warn(f"DomeLight {prim.name}: environment map not decoded, using the uniform colour")
-            desc.lights.append(dome_light(_lux_emission(prim)))
+            desc.lights.append(dome_light(_lux_emission(prim), env))
         return world
 
     def traverse(root_prims, root_world):

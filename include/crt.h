@@ -230,18 +230,62 @@ typedef struct CrtMaterial {
 } CrtMaterial;
 void crt_material_default(CrtMaterial *m);                          /* OpenPBR::default   openpbr.rs:130-173 */
 
-enum { CRT_LIGHT_SPHERE = 0, CRT_LIGHT_RECT = 1, CRT_LIGHT_DISTANT = 2, CRT_LIGHT_DOME = 3 };
+enum { CRT_LIGHT_SPHERE = 0, CRT_LIGHT_RECT = 1, CRT_LIGHT_DISTANT = 2, CRT_LIGHT_DOME = 3, CRT_LIGHT_DOME_MAP = 4 };
 /* AreaLight{shape, material, geom_id} (light.rs:156-163) with SphereShape (:22-25) / RectShape (:52-57).
  * The two lights at infinity reuse the record, already in their derived form and with geom_id = CRT_INVALID_ID:
  *   DISTANT (DistantLight, light.rs:234-318): normal = unit travel direction, radiance = irradiance,
  *           radius = cos(half angle), center[0] = cone solid angle 2*pi*(1 - cos(half angle))   (light.rs:255-266)
- *   DOME    (DomeLight without an environment map, light.rs:320-390): radiance = tint; uniform over the sphere. */
+ *   DOME    (DomeLight without an environment map, light.rs:320-390): radiance = tint; uniform over the sphere.
+ *   DOME_MAP (DomeLight with an EnvironmentMap): radiance = tint, center[0] = the BITS of the environment's id
+ *           (crt_light_dome_mapped fills the record). An id, never an address: the kernels look it up in the library's
+ *           own table of live environments, and an id that names none answers None. The id is a WORD, not a number:
+ *           copy it bitwise (memcpy, a u32 view). Its bits are always those of a normal finite float, so a copy through
+ *           a float register survives flush-to-zero and NaN quieting, but arithmetic on it means nothing. */
 typedef struct CrtLight {
   uint32_t kind; uint32_t geom_id;
   float radiance[3];
   float center[3]; float radius;
   float origin[3]; float edge_u[3]; float edge_v[3]; float normal[3];
 } CrtLight;
+
+/* ---- environment maps: EnvironmentMap (environment.rs:106-215) and the orientation of its DomeLight (light.rs:320-337) ----
+ * A lat-long HDRI with the 2-D sampling distribution built over it (luminance x sin theta per texel; one Distribution1D
+ * over the rows and one per row over the columns, environment.rs:39-66, :120-144), ref-counted like Arc<EnvironmentMap>.
+ * The dome's orientation is part of the object: light_to_world and its inverse (glam Mat3A::inverse). */
+typedef struct CrtEnvironment CrtEnvironment;
+/* EnvironmentMap::new + DomeLight::new's orientation (environment.rs:120-144, light.rs:330-337). rgb: HOST pixels, row 0 at
+ * +Y, 3 floats per texel (copied). light_to_world: Mat3A as 9 floats, columns x, y, z; NULL = identity. Touches no device:
+ * the image is uploaded on first device use. NULL with the reason in crt_last_error when width or height is 0 or above
+ * 16384 (or the image would pass 4 GiB), rgb is NULL, a texel is not finite (the reference accepts those and poisons its
+ * CDF), light_to_world has no finite inverse, all 16 environment slots are live, or memory runs out. Negative texels are
+ * accepted as upstream: weight 0, radiance as authored. */
+CrtEnvironment *crt_environment_new(uint32_t width, uint32_t height, const float *rgb, const float light_to_world[9]);
+/* Upload and threads: the image of an environment is uploaded the first time the device needs it — inside
+ * crt_renderer_new for the environments its lights name, else inside the first crt_light_sample_n / _pdf_n / _escaped_n
+ * call made while it is live. That call then allocates device memory and copies synchronously before it launches, which a
+ * stream capture does not allow: make one such call (n = 1 will do) before capturing. Every crt_light_*_n call takes a
+ * process-wide lock for the time it checks the table of live environments (a few loads once everything is uploaded);
+ * the launches themselves stay asynchronous on the caller's stream. crt_environment_free of the last reference
+ * synchronises the device before the image goes. */
+/* drop(Arc<EnvironmentMap>): the caller's reference. A renderer keeps the environments its lights name alive; once the
+ * last reference is gone the id answers None (some = 0) from the light functions. */
+void crt_environment_free(CrtEnvironment *env);
+/* Host pointers to what EnvironmentMap::new built (environment.rs:106-115), valid while `env` lives, for tests — as
+ * crt_scene_image_prims hands out the primitive records. conditional_func: height x width; conditional_cdf: height x
+ * (width + 1); conditional_integral: height; marginal_func: height; marginal_cdf: height + 1. image: the bytes the
+ * device reads (kernels/envmap.hip.h). */
+typedef struct CrtEnvironmentTables {
+  uint32_t width, height;
+  uint32_t id; float marginal_integral;
+  const float *marginal_func, *marginal_cdf;
+  const float *conditional_func, *conditional_cdf, *conditional_integral;
+  float light_to_world[9], world_to_light[9];
+  const void *image; size_t image_bytes;
+} CrtEnvironmentTables;
+int crt_environment_tables(const CrtEnvironment *env, CrtEnvironmentTables *out);
+/* DomeLight::new(tint, Some(map), light_to_world) (light.rs:330-337): kind CRT_LIGHT_DOME_MAP, radiance = tint, geom_id =
+ * CRT_INVALID_ID, center[0] = the bits of the environment's id; every other field 0. */
+int crt_light_dome_mapped(CrtLight *out, const float tint[3], const CrtEnvironment *env);
 
 /* Camera (camera.rs:8-25), already in its derived form. */
 typedef struct CrtCamera {
@@ -305,7 +349,8 @@ int crt_material_eval_n(const CrtMaterial *d_materials, size_t n_materials, cons
 int crt_material_emitted_n(const CrtMaterial *d_materials, size_t n_materials, const CrtShadeQuery *d_queries, size_t n,
                            float *d_rgb, void *stream);
 /* Light::sample_li(from, u, v) -> Option<LightSample>                           light.rs:126, AreaLight :191-204 (sphere
- * :27-36, rect :69-81), DistantLight :285-298, uniform DomeLight :358-383. */
+ * :27-36, rect :69-81), DistantLight :285-298, DomeLight :358-383 (uniform, and mapped: environment.rs:181-190).
+ * A DOME_MAP record whose id names no live environment answers None. */
 int crt_light_sample_n(const CrtLight *d_lights, size_t n_lights, const CrtLightQuery *d_queries, size_t n,
                        CrtLightSample *d_out, void *stream);
 /* Light::pdf_at_point(from, light_point) -> f32                                 light.rs:132, AreaLight :206-208 ->
@@ -313,7 +358,10 @@ int crt_light_sample_n(const CrtLight *d_lights, size_t n_lights, const CrtLight
 int crt_light_pdf_n(const CrtLight *d_lights, size_t n_lights, const CrtLightQuery *d_queries, size_t n, float *d_pdf,
                     void *stream);
 /* Light::escaped(from, direction) -> Option<(radiance, pdf)>                    light.rs:141-146, :300-303, :385-388;
- * None (some = 0) for area lights and for directions the light does not cover. out.direction = the query's. */
+ * None (some = 0) for area lights and for directions the light does not cover. out.direction = the query's. A mapped
+ * dome covers every direction: radiance = tint * the map's nearest texel along world_to_light * direction, pdf = the map's
+ * solid-angle density there (light.rs:340-355, environment.rs:171-176, :194-214); None only when its id names no live
+ * environment. */
 int crt_light_escaped_n(const CrtLight *d_lights, size_t n_lights, const CrtLightQuery *d_queries, size_t n,
                         CrtLightSample *d_out, void *stream);
 
