@@ -171,7 +171,7 @@ ABI_SYMBOLS = [
     "crt_film_read", "crt_film_clear", "crt_renderer_active_pixels", "crt_renderer_sample_counts", "crt_render_stats", "crt_renderer_profile", "crt_renderer_profile_read",
     "crt_render_samples_stats", "crt_version", "crt_last_error", "crt_device_info",
     "crt_scene_primitive_extents", "crt_scene_traversal_error", "crt_thread_release", "crt_renderer_shade_class_stats", "crt_renderer_pipeline", "crt_renderer_lanes", "crt_scene_image_check",
-    "crt_scene_engine_select", "crt_scene_image_prims",
+    "crt_scene_engine_select", "crt_scene_image_prims", "crt_scene_root_touched_n",
     "crt_material_scatter_n", "crt_material_eval_n", "crt_material_emitted_n", "crt_light_sample_n", "crt_light_pdf_n",
     "crt_light_escaped_n",
     "crt_shard_padded_count", "crt_gather_plan_new", "crt_gather_plan_free", "crt_gather_plan_padded_count",
@@ -234,6 +234,8 @@ def lib():
         L.crt_scene_image_check.argtypes = [vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "crt_scene_image_prims"):  # absent from older A/B variant libraries
         L.crt_scene_image_prims.argtypes = [vp, up, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "crt_scene_root_touched_n"):  # absent from older A/B variant libraries
+        L.crt_scene_root_touched_n.argtypes = [vp, fp, C.c_size_t, C.c_float, C.c_float, C.POINTER(C.c_uint8), up]
     if hasattr(L, "crt_scene_engine_select"):  # absent from older A/B variant libraries
         L.crt_scene_engine_select.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32)]
     L.crt_scene_tree.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
@@ -436,6 +438,18 @@ class Scene:
             _check(lib().crt_scene_image_prims(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)),
                    "crt_scene_image_prims")
         return out
+
+    def root_touched(self, rays, t_min=0.001, t_max=float("inf")):
+        """Host-only: the renderer's root cull as a function (crt.h, crt_scene_root_touched_n). rays: [n, >= 6] float32
+        (origin, direction) -> (bool [n]: the ray touches a child box of the image's root node, the root's node index or
+        None for an empty scene). Needs no GPU."""
+        import numpy as np
+        r6 = np.ascontiguousarray(np.asarray(rays, dtype=np.float32)[:, :6])
+        out = np.zeros(len(r6), np.uint8)
+        root = C.c_uint32()
+        _check(lib().crt_scene_root_touched_n(self.h, _fp(r6), len(r6), t_min, t_max,
+                                              out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(root)), "crt_scene_root_touched_n")
+        return out.astype(bool), (None if root.value == 0xFFFFFFFF else int(root.value))
 
     def engine_select(self, want_wide=-1):
         """Which traversal-engine instance the library selects for this scene's image (crt.h, crt_scene_engine_select;
@@ -857,11 +871,13 @@ class Renderer:
         return {n: (int(w[k]), (l[k] / (64.0 * w[k])) if w[k] else 0.0) for k, n in enumerate(self.SHADE_CLASSES)}
 
     def pipeline(self):
-        """{'fused', 'wide', 'shade_pipe', 'grid'}: the launch pipeline chosen for this scene (crt.h, crt_renderer_pipeline);
-        shade_pipe: the last batch's shade launches were the pipelined four-wave instance."""
+        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'grid'}: the launch pipeline chosen for this scene (crt.h,
+        crt_renderer_pipeline); shade_pipe: the last batch's shade launches were the pipelined four-wave instance;
+        root_cull: its generate launches finished the camera rays that miss every child of the root."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
-        return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), grid=int(out[2]))
+        return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
+                    grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""

@@ -340,6 +340,10 @@ int crt_scene_image_prims(CrtScene *s, uint32_t *words16, size_t cap_prims, size
     return (int)CRT_OK;
   });
 }
+int crt_scene_root_touched_n(CrtScene *s, const float *rays6, size_t n, float t_min, float t_max, uint8_t *touched, uint32_t *root) {
+  if (!s || !root || (n && (!rays6 || !touched))) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_scene_root_touched_n", [&] { return scene_root_touched(*s->p, rays6, n, t_min, t_max, touched, root); });
+}
 int crt_scene_engine_select(CrtScene *s, int want_wide, uint32_t out[8]) {
   if (!s || !out) return CRT_ERR_BAD_ARG;
   try {

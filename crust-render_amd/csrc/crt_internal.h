@@ -158,6 +158,33 @@ CRT_HOST_DEVICE inline void flat_tri_normal(const float v[9], float n[3]) {
   n[0] = x / len; n[1] = y / len; n[2] = z / len;
 }
 
+// "Does this ray touch any child of this node": the node step of the traversal engine (kernels/traverse_pool.hip.h, the
+// slab4 loop; RaySlab::slab4, bvh.rs:790-808) as one predicate on a device-form node (an empty lane's child word is
+// CRT_INVALID_ID), with the engine's own expressions in the engine's order: the reciprocal direction of setup_ray
+// (safe_inv3, bvh.rs:662-668), t0 = (lo - o) * inv, t1 = (hi - o) * inv, the min / max chains seeded with t_min / t_max,
+// lane on iff tn <= tf. Identical expressions, so the two agree on every ray, NaN and infinite directions included
+// (fminf / fmaxf return the operand that is a number on both sides). The renderer's generate stage asks it of the
+// image's root for every camera ray (pathtrace.hip, generate_segment_cull): a ray that touches no child of the root is
+// a ray the engine reports as a miss after exactly one node step. One source for host and device, as flat_tri_normal.
+CRT_HOST_DEVICE inline float safe_inv(float d) {
+  const float TINY = 1e-20f, HUGE_ = 1e20f;
+  return fabsf(d) < TINY ? copysignf(HUGE_, d) : 1.0f / d;
+}
+CRT_HOST_DEVICE inline bool node_touched(const float bmin[3][4], const float bmax[3][4], const uint32_t child[4], float ox,
+                                         float oy, float oz, float dx, float dy, float dz, float t_min, float t_max) {
+  const float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
+  bool any = false;
+  for (int l = 0; l < 4; l++) {
+    const float t0x = (bmin[0][l] - ox) * ix, t1x = (bmax[0][l] - ox) * ix;
+    const float t0y = (bmin[1][l] - oy) * iy, t1y = (bmax[1][l] - oy) * iy;
+    const float t0z = (bmin[2][l] - oz) * iz, t1z = (bmax[2][l] - oz) * iz;
+    const float tn = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)), t_min);
+    const float tf = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)), t_max);
+    any = any || ((tn <= tf) && child[l] != 0xFFFFFFFFu);
+  }
+  return any;
+}
+
 struct DevInstance {  // 64 bytes: what an instance entry reads (half a cache line; 40 000 placements stay L2-resident)
   float w2l[12];      // cached world-to-local at time 0 (prim.rs:266); its matrix3 transposed is the normal matrix (:267)
   uint32_t root;      // absolute node index of the instanced scene's root
@@ -362,7 +389,7 @@ struct Knobs {
   // engine choice
   int wide = -1;              // CRT_WIDE
   // renderer
-  int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, shade_wide = -1, shade_pipe = 1, fused = -1;
+  int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, root_cull = -1, shade_wide = -1, shade_pipe = 1, fused = -1;
   int mat_derived = 1;        // CRT_MAT_DERIVED: 0 = the shade kernels compute the per-material constants at every vertex again
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
@@ -396,6 +423,10 @@ struct Scene : std::enable_shared_from_this<Scene> {
 int scene_image_check(const Scene &scene, uint64_t out[8]);
 // Host-only: the image's primitive records (scene.cpp).
 int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out);
+// Host-only: node_touched on the root node of the image this scene would upload, for n rays of six floats (origin,
+// direction): out[i] = 1 when ray i touches a child of the root. *root = the image's root (CRT_INVALID_ID: an empty
+// scene, every out[i] = 0).
+int scene_root_touched(const Scene &scene, const float *rays6, size_t n, float t_min, float t_max, uint8_t *out, uint32_t *root);
 // Host-only: select_engine on the image this scene would upload, verified against a census of the image (scene.cpp).
 int scene_engine_select(const Scene &scene, int want_wide, uint32_t out[8]);
 

@@ -204,8 +204,13 @@ struct Params {
   uint32_t class_stats;         // count Counters::cls_* in the vertex step (diagnostic, off by default)
   // Per-stage pipeline, pinhole camera, no motion blur: a camera path is the 16 bytes (direction, sampler pattern) in
   // plane `a` — its origin is the camera's, its throughput 1, its radiance 0, pixel / sample / depth follow from the slot
-  // number (generate_segment). Set per batch by Renderer::render.
+  // number (generate_segment). Set per batch by Renderer::render. 2: the compact form under the root cull — the survivors
+  // are compacted, so a slot no longer names its sample: plane `d` is written too and read back (compact_camera_path).
   uint32_t cam_compact;
+  // Per-stage launches: generate finishes every camera ray that touches no child box of the root node on the spot — the
+  // sky gradient into the staging film, the counters the miss step feeds — and appends only the others to its segment
+  // (generate_segment_cull). Set per batch by Renderer::render_lane, which holds the rule.
+  uint32_t root_cull;
   // The library's table of live environments (environment.cpp), read by the mapped-dome instances only (k_shade_env):
   // a CRT_LIGHT_DOME_MAP record names its environment by id. nullptr when the light list holds no such record.
   const EnvSlot *envs;
@@ -232,6 +237,13 @@ __device__ __forceinline__ float bounce_weight(int s, float bounce_pdf, float li
 __device__ __forceinline__ V3 sky_gradient(V3 unit_direction) {
   const float t = 0.5f * (unit_direction.y + 1.0f);
   return v3(1.0f, 1.0f, 1.0f) * (1.0f - t) + v3(0.5f, 0.7f, 1.0f) * t;
+}
+// A path that leaves a scene without lights at infinity ends on the sky gradient (tracer.rs:1321-1342): the one expression
+// of the miss steps of shade and of generate's root cull, so the three write the same bits.
+__device__ __forceinline__ V3 escaped_to_sky(V3 rd, V3 beta, V3 L) {
+  const V3 unit_direction = normalize(rd);
+  const V3 background = splat(0.0f) + sky_gradient(unit_direction);
+  return L + beta * background;
 }
 template <bool ENV = false>
 __device__ __forceinline__ V3 escaped_background(const CrtLight *lights, uint32_t n_lights, int strategy,
@@ -414,12 +426,17 @@ __device__ __forceinline__ size_t camera_slot_sample(size_t k) {
 
 // A compact camera path (Params::cam_compact) read back: direction and pattern from plane `a`, origin = the pinhole
 // camera's (camera_get_ray with no lens offset: origin + 0), pixel and sample from the slot's sample number (< 2^31:
-// ensure_buffers). D = plane d's words as generate would have written them.
+// ensure_buffers). D = plane d's words as generate would have written them — under the root cull (cam_compact == 2) the
+// words generate DID write: the caller has read plane d into D, the slot of a compacted survivor says nothing. PLANE_D:
+// the instance holds that form (the simple-material shade kernels; the general ones are at their register limit and
+// run the full form under the root cull instead — Renderer::render_lane).
+template <bool PLANE_D>
 __device__ __forceinline__ void compact_camera_path(const Params &P, uint32_t k, float4 a, float4 &A, float4 &B, uint4 &D) {
-  const uint32_t g = (uint32_t)camera_slot_sample(k);
   const V3 o = ld3(P.camera.origin) + splat(0.0f);
   A = make_float4(o.x, o.y, o.z, a.x);
   B = make_float4(a.y, a.z, 1.0f, 1.0f);
+  if (PLANE_D && P.cam_compact == 2) return;  // uniform
+  const uint32_t g = (uint32_t)camera_slot_sample(k);
   D = make_uint4(__float_as_uint(a.w), g % P.n_act, (P.max_depth & 0xffffu) << 16, g / P.n_act);
 }
 
@@ -478,10 +495,89 @@ __device__ __forceinline__ void generate_segment(const Params &P, const PathSoA 
     if (blockIdx.x == 0) atomicAdd(&C->stats[0], (unsigned long long)total);  // camera_rays (tracer.rs:585)
   }
 }
+// ---- generate with the ROOT CULL (per-stage launches only; Renderer::render_lane holds the rule) ----
+// On an open frame nearly every camera ray that escapes does so at the root: it tests the root's four child boxes,
+// touches none and leaves (cornellbox 1080p: 44 % of the camera rays; 16 of 20 736 escaping rays get past the root). Such
+// a ray used to be written here, fetched, set up and stepped once by the first extend, classified, queued and finished by
+// a miss step of the first shade. Its whole traversal is four slab tests on wave-uniform data, and its origin and
+// direction are in registers here: node_touched (crt_internal.h — the engine's node step, expression for expression)
+// decides, and a ray it calls a miss is finished on the spot with the miss step's arithmetic (escaped_to_sky) and the
+// miss step's counters. The ray IS traced — its traversal is the root step, done where the ray is born — so closest_hit,
+// escaped and the image keep their values. Survivors are appended to the front of the segment with the workgroup's LDS
+// counter, as shade appends its survivors; a survivor's slot then no longer names its sample, so the compact form
+// carries plane `d` as well (Params::cam_compact == 2). The slot loop is uniform: every wave appends in every round.
+constexpr bool kRootCullBuild = kBins == 1 && !kRegenFirst;
+__device__ __forceinline__ void generate_segment_cull(const Params &P, const PathSoA &S, Counters *C, uint32_t sample_begin,
+                                                      uint32_t n_samples, uint32_t *sobol_tab /* kSobolLdsWords */, float4 *staging) {
+  // the root's bounds and child words: wave-uniform, read once ahead of every store of this kernel (scalar loads)
+  float bmin[3][4], bmax[3][4];
+  uint32_t child[4];
+  {
+    const WideNode &root = P.scene.nodes[P.scene.root];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int l = 0; l < 4; l++) { bmin[a][l] = root.bmin[a][l]; bmax[a][l] = root.bmax[a][l]; }
+#pragma unroll
+    for (int l = 0; l < 4; l++) child[l] = root.child[l];
+  }
+  __shared__ uint32_t cull_ctr[2];  // survivors appended | camera rays finished here
+  if (threadIdx.x < 2) cull_ctr[threadIdx.x] = 0;
+  sobol_tables_init(sobol_tab);  // ends with a workgroup barrier
+  const size_t total = (size_t)P.n_act * n_samples;
+  const size_t seg0 = (size_t)blockIdx.x * kBins * P.seg_cap;  // camera rays are coherent as dealt: all in bin 0
+  const bool compact = CRT_CAM_COMPACT_BUILD && P.cam_compact != 0;  // uniform
+  uint32_t n_culled = 0;
+  for (size_t k0 = 0; k0 < P.seg_cap; k0 += kBlock) {  // uniform: seg_cap is a multiple of the workgroup's width
+    if (camera_slot_sample(k0) >= total) break;        // uniform: this round's first sample is past the end, so are all later ones
+    const size_t g = camera_slot_sample(k0 + threadIdx.x);
+    CameraSample cs;
+    cs.o = splat(0.0f); cs.d = splat(0.0f); cs.time = 0.0f; cs.pattern = 0; cs.pix = 0; cs.sl = 0;
+    bool keep = false;
+    if (g < total) {  // the last round's ragged end: lanes past it append nothing
+      cs = camera_sample(P, g, sample_begin, sobol_tab);
+      // t_min / t_max as extend_segment's fetch sets them
+      keep = node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);
+      if (!keep) {  // tracer.rs:1321-1342 with L = 0, beta = 1: the first shade's miss step
+        const V3 L = escaped_to_sky(cs.d, splat(1.0f), splat(0.0f));
+        st_nt(&staging[cs.sl * P.n_act + cs.pix], make_float4(L.x, L.y, L.z, 0.0f));
+        n_culled++;
+      }
+    }
+    const size_t i = seg0 + seg_append(keep, &cull_ctr[0]);
+    if (keep) {
+      const uint4 D = make_uint4(cs.pattern, cs.pix, (P.max_depth & 0xffffu) << 16, cs.sl);
+      if (compact) {
+        st_nt(&S.a[i], make_float4(cs.d.x, cs.d.y, cs.d.z, __uint_as_float(cs.pattern)));
+        st_nt(&S.d[i], D);
+      } else {
+        st_nt(&S.a[i], make_float4(cs.o.x, cs.o.y, cs.o.z, cs.d.x));
+        st_nt(&S.b[i], make_float4(cs.d.y, cs.d.z, 1.0f, 1.0f));
+        st_nt(&S.d[i], D);
+        if (P.has_motion) st_nt(&S.time[i], cs.time);
+      }
+    }
+  }
+  add_stat(&cull_ctr[1], n_culled);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int b = 0; b < kBins; b++) {
+      C->seg[0][blockIdx.x * kBins + b] = b == 0 ? cull_ctr[0] : 0;
+      C->seg[1][blockIdx.x * kBins + b] = 0;
+    }
+    C->shadow[blockIdx.x] = 0;
+    if (blockIdx.x == 0) atomicAdd(&C->stats[0], (unsigned long long)total);  // camera_rays (tracer.rs:585)
+    if (cull_ctr[1]) {  // closest_hit and escaped, at the indices shade's miss step feeds
+      atomicAdd(&C->stats[1], (unsigned long long)cull_ctr[1]);
+      atomicAdd(&C->stats[6], (unsigned long long)cull_ctr[1]);
+    }
+  }
+}
 __global__ __launch_bounds__(kBlock) void k_generate(Params P, PathSoA S, Counters *C, uint32_t sample_begin,
-                                                     uint32_t n_samples) {
+                                                     uint32_t n_samples, float4 *staging) {
   __shared__ uint32_t sobol_tab[kSobolLdsWords];
-  generate_segment(P, S, C, sample_begin, n_samples, sobol_tab, false);
+  if (kRootCullBuild && P.root_cull) generate_segment_cull(P, S, C, sample_begin, n_samples, sobol_tab, staging);  // uniform
+  else generate_segment(P, S, C, sample_begin, n_samples, sobol_tab, false);
 }
 
 // ---- extend: World::intersect (rt_world.rs:207-232) for every live path ----
@@ -573,6 +669,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
   // (cornellbox_guided) where the unlit one gains 1 % (profiles/README.md). The host sets Params::cam_compact for
   // unlit scenes only and runs a deduplicated table (Params::mat_index) through the three-wave shade kernel.
   constexpr bool COMPACT = CRT_CAM_COMPACT_BUILD && !LIT;
+  constexpr bool COMPACT_D = COMPACT && SIMPLE;  // ... with plane d read back (root cull): the simple-material instances only
   constexpr bool MAT_INDEX = CRT_MAT_INDEX_BUILD && ARENA != kArenaWide;
   __shared__ uint32_t lds_ctr[10];  // [1] shadow requests, [2..8] statistics
   __shared__ uint32_t out_n[kBins];  // survivors per direction bin
@@ -671,9 +768,10 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
         float4 A, B, Cc = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
         if (COMPACT && first && P.cam_compact) {  // uniform
           float4 a = S.a[i_c];
+          if (COMPACT_D && P.cam_compact == 2) D = S.d[i_c];  // uniform: the root cull's survivors carry their pixel and sample
           asm volatile("" : "+v"(a.x));
           if (STAMPS) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a.x) : : "memory");
-          compact_camera_path(P, k_c, a, A, B, D);
+          compact_camera_path<COMPACT_D>(P, k_c, a, A, B, D);
         } else if (!(kRegenFirst && first)) {
           D = S.d[i_c]; A = S.a[i_c]; B = S.b[i_c];
           if (!first) Cc = S.c[i_c];
@@ -700,9 +798,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
           V3 L = v3(Cc.y, Cc.z, Cc.w);
           s_closest++;
           s_esc++;
-          const V3 unit_direction = normalize(rd);
-          const V3 background = splat(0.0f) + sky_gradient(unit_direction);
-          L = L + beta * background;
+          L = escaped_to_sky(rd, beta, L);
           st_nt(&staging[(D.w & 0xffffu) * P.n_act + D.y], make_float4(L.x, L.y, L.z, 0.0f));
         } else {
           pending = true;
@@ -754,7 +850,8 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
       float4 A, B, Cc = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
       uint4 D;
       if (COMPACT && first && P.cam_compact) {  // uniform
-        compact_camera_path(P, k_in, S.a[i], A, B, D);
+        if (COMPACT_D && P.cam_compact == 2) D = S.d[i];  // uniform (root cull)
+        compact_camera_path<COMPACT_D>(P, k_in, S.a[i], A, B, D);
         time = 0.0f;
       } else if (!(kRegenFirst && first)) {
         A = S.a[i]; B = S.b[i]; D = S.d[i];
@@ -1110,6 +1207,7 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
   __syncthreads();
   const uint32_t seg0 = blockIdx.x * P.seg_cap;  // kBins == 1: slot of the k-th live path = seg0 + k
   const bool compact = CRT_CAM_COMPACT_BUILD && first && P.cam_compact;  // uniform: camera paths are plane a's 16 bytes
+  const bool compact_d = compact && P.cam_compact == 2;                  // uniform: ... and plane d's (root cull: compacted survivors)
   uint32_t s_closest = 0, s_vertices = 0, s_rr_t = 0, s_rr_k = 0, s_esc = 0, s_depth = 0;
   unsigned long long t_acc[7] = {0, 0, 0, 0, 0, 0, 0}, t0 = 0;
   auto lap = [&](int slot) {
@@ -1132,6 +1230,8 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
         B = reinterpret_cast<const float4 *>(stg + 256)[lane];
         D = reinterpret_cast<const uint4 *>(stg + 768)[lane];
         if (!first) Cc = reinterpret_cast<const float4 *>(stg + 512)[lane];
+      } else if (compact_d) {
+        D = reinterpret_cast<const uint4 *>(stg + 768)[lane];
       }
       if (kind == 1 && CRT_SHADE_PIPE_HIT_REGS) {
         hh = H.h[seg0 + k_in];
@@ -1175,6 +1275,8 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
         lds_dma16(&S.b[i_n], stg + 256);
         lds_dma16(&S.d[i_n], stg + 768);
         if (!first) lds_dma16(&S.c[i_n], stg + 512);
+      } else if (compact_d) {
+        lds_dma16(&S.d[i_n], stg + 768);
       }
       if (kind_n == 1 && !CRT_SHADE_PIPE_HIT_REGS) {
         lds_dma16(&H.h[i_n], stg + 1024);
@@ -1188,16 +1290,14 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
     if (kind == 2) {
       // ---- MISS step (tracer.rs:1321-1342, :1123-1149): the path ends on the sky gradient, or at the depth limit ----
       if (active) {
-        if (compact) compact_camera_path(P, k_in, A, A, B, D);
+        if (compact) compact_camera_path<true>(P, k_in, A, A, B, D);
         const int remaining = (int)(D.z >> 16);
         const V3 rd = v3(A.w, B.x, B.y), beta = v3(B.z, B.w, Cc.x);
         V3 L = v3(Cc.y, Cc.z, Cc.w);
         if (remaining > 0) {
           s_closest++;
           s_esc++;
-          const V3 unit_direction = normalize(rd);
-          const V3 background = splat(0.0f) + sky_gradient(unit_direction);
-          L = L + beta * background;
+          L = escaped_to_sky(rd, beta, L);
         } else {  // depth exhausted: nothing is added
           s_depth++;
           if ((D.w & kPrevValid) != 0) s_closest++;
@@ -1212,7 +1312,7 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
       uint32_t meta = 0, aux = 0, pix = 0, pattern = 0;
       bool n_delta = false;
       if (active) {
-        if (compact) compact_camera_path(P, k_in, A, A, B, D);
+        if (compact) compact_camera_path<true>(P, k_in, A, A, B, D);
         const V3 ro = v3(A.x, A.y, A.z), rd = v3(A.w, B.x, B.y);
         beta = v3(B.z, B.w, Cc.x);
         L = v3(Cc.y, Cc.z, Cc.w);
@@ -1561,6 +1661,34 @@ struct Renderer {
   // names — flat engine copy or, for direct-leaf images, the direct one; profiles/README.md).
   bool prefer_stage = false;
   bool cam_compact_ok = true;  // CRT_CAM_COMPACT
+  int root_cull_knob = -1;     // CRT_ROOT_CULL: 0 = generate never finishes a camera ray, 1 = wherever the rule allows (A/B, tests)
+  // What the cull can save grows with the share of the frame that shows background; what it costs does not: generate's
+  // slab tests and compaction, plane d beside the compact form (measured: profiles/README.md — cornellbox, 0.44 of its
+  // camera rays culled, +1.7 %; openpbr_showcase, 0.23, +1 %; veach_mis, 0.06, and the two scenes that fill their frame
+  // lose 1-3 %). So the renderer looks first: the root step of the pixel-centre rays of a 32 x 18 grid over the frame,
+  // through the lens centre, on the host (root_miss_share, at creation), and culls only where at least an eighth of them
+  // miss every child of the root — between the share that lost and the shares that won.
+  float root_miss_share = 0.0f;
+  static constexpr float kRootCullMinShare = 0.125f;
+  void estimate_root_miss_share() {
+    root_miss_share = 0.0f;
+    if (!scene || scene->bvh.wide.empty()) return;
+    const WideNode &nd = scene->bvh.wide[0];  // the committed tree's root (bvh.rs:442-447): the image's root node, child words apart
+    uint32_t child[4];
+    for (int l = 0; l < 4; l++) child[l] = (nd.flags & (1u << l)) ? 0u : kInvalid;
+    const CrtCamera &c = P.camera;
+    constexpr int GW = 32, GH = 18;
+    int missed = 0;
+    for (int j = 0; j < GH; j++)
+      for (int i = 0; i < GW; i++) {
+        const float sx = ((float)i + 0.5f) / (float)GW, sy = ((float)j + 0.5f) / (float)GH;
+        float d[3];
+        for (int a = 0; a < 3; a++) d[a] = c.lower_left[a] + c.horizontal[a] * sx + c.vertical[a] * sy - c.origin[a];
+        if (!node_touched(nd.bmin, nd.bmax, child, c.origin[0], c.origin[1], c.origin[2], d[0], d[1], d[2], 0.001f, CRT_INF)) missed++;
+      }
+    root_miss_share = (float)missed / (float)(GW * GH);
+  }
+  bool root_culled = false;    // the LAST batch's generate launches ran the root cull (crt_renderer_pipeline)
   int shade_wide = -1;            // CRT_SHADE_WIDE: 0 = the three-wave shade kernels even beside four-wave traversal kernels (A/B)
   size_t max_batch_slots = 0;     // CRT_MAX_BATCH_SLOTS (tests): ensure_buffers fails above this many slots; 0 = no limit
   int tail_from = 12;             // CRT_TAIL_FROM: the bounce from which a per-stage batch finishes in one fused launch
@@ -1792,6 +1920,17 @@ struct Renderer {
     // camera paths as 16-byte records: per-stage launches of an UNLIT scene, pinhole camera, static scene
     // (CRT_CAM_COMPACT=0: A/B, tests)
     p.cam_compact = (CRT_CAM_COMPACT_BUILD && !fused && cam_compact_ok && P.n_lights == 0 && !(P.camera.lens_radius > 0.0f) && !P.has_motion) ? 1u : 0u;
+    // The root cull (generate_segment_cull): per-stage launches of an image whose root is a node, when a camera ray that
+    // escapes ends on the sky gradient — a depth limit above 0 and no light at infinity (their escaped rays take the
+    // vertex step) — and where the frame shows enough background for it to pay (root_miss_share; CRT_ROOT_CULL=1 skips
+    // that estimate). Not in the stats build: its kernels count the node visits the oracle counts. Lens cameras, moving
+    // instances, adaptive stopping and curve images qualify: the root step depends on none of them. The compact form
+    // then carries plane d (cam_compact == 2) where the shade instances hold that form: simple-material tables. The
+    // general instances sit at their register limit (k_shade<2, false, false, false, false> gained three spilled
+    // registers with it) and read the full form instead.
+    root_culled = kRootCullBuild && root_cull_knob != 0 && (root_cull_knob > 0 || root_miss_share >= kRootCullMinShare) && !fused && !d_tstats && P.scene.root != kInvalid && P.max_depth > 0 && !P.has_inf_lights;
+    p.root_cull = root_culled ? 1u : 0u;
+    if (root_culled && p.cam_compact) p.cam_compact = mats_kind == 0 ? 2u : 0u;
     // the film fold: plain sum, or with the luminance statistics and the stopping rule, then the new active list
     auto fold = [&]() -> int {
       if (!fold_here) return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : CRT_ERR_NO_DEVICE;  // the caller folds the lanes in order
@@ -1866,7 +2005,7 @@ struct Renderer {
       });
       return fold();
     }
-    timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples); });
+    timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples, staging); });
     int cur = 0;
     // The TAIL: from bounce `tail_from` on, what is left of the batch — roulette has ended all but a few paths per ten
     // thousand by then (bench: 6.6 M of 531 M rays at bounce 4, 0.1 M at bounce 6) — runs as ONE launch of the fused
@@ -2177,6 +2316,8 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   r.prefer_stage = true;
   if (knobs.prefer_stage >= 0) r.prefer_stage = knobs.prefer_stage != 0;  // the A/B knobs (crt_internal.h, Knobs): CRT_PREFER_STAGE ...
   r.cam_compact_ok = knobs.cam_compact != 0;
+  r.root_cull_knob = knobs.root_cull;
+  r.estimate_root_miss_share();
   r.noclassify_from = knobs.noclassify_from;
   r.shade_pipe = knobs.shade_pipe;
   r.mat_derived = knobs.mat_derived != 0;
@@ -2320,7 +2461,8 @@ int crt_renderer_set_lanes(CrtRenderer *r, int lanes) {
 int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   if (!r || !out) return CRT_ERR_BAD_ARG;
   out[0] = r->r.fused ? 1u : 0u;
-  out[1] = ((!r->r.fused && r->r.wide) ? 1u : 0u) | ((!r->r.fused && r->r.shade_piped) ? 2u : 0u);
+  out[1] = ((!r->r.fused && r->r.wide) ? 1u : 0u) | ((!r->r.fused && r->r.shade_piped) ? 2u : 0u) |
+           ((!r->r.fused && r->r.root_culled) ? 4u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

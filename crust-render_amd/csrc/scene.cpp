@@ -233,6 +233,7 @@ Knobs read_knobs() {
   if (num("CRT_SIMPLE", v)) k.simple = v != 0;
   if (num("CRT_PREFER_STAGE", v)) k.prefer_stage = v != 0;
   if (num("CRT_CAM_COMPACT", v)) k.cam_compact = v != 0;
+  if (num("CRT_ROOT_CULL", v)) k.root_cull = v != 0 ? 1 : 0;  // unset: where the renderer's estimate says it pays
   if (num("CRT_SHADE_WIDE", v)) k.shade_wide = v != 0;
   if (num("CRT_SHADE_PIPE", v)) k.shade_pipe = v != 0;
   if (num("CRT_MAT_DERIVED", v)) k.mat_derived = v != 0;
@@ -730,6 +731,25 @@ int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out) {
   const int rc = flatten_image(scene, im);
   if (rc != CRT_OK) return rc;
   out.swap(im.f.prims);
+  return CRT_OK;
+}
+
+// Host-only: the renderer's root cull (crt_internal.h, node_touched) asked of the image's root node on the host — the
+// function the generate kernel runs, compiled for the CPU, so a test can hold it against the oracle's traversal.
+int scene_root_touched(const Scene &scene, const float *rays6, size_t n, float t_min, float t_max, uint8_t *out, uint32_t *root) {
+  FlatImage im;
+  const int rc = flatten_image(scene, im);
+  if (rc != CRT_OK) return rc;
+  *root = im.me.root;
+  if (im.me.root == CRT_INVALID_ID) {
+    for (size_t i = 0; i < n; i++) out[i] = 0;
+    return CRT_OK;
+  }
+  const WideNode &nd = im.f.nodes[im.me.root];
+  for (size_t i = 0; i < n; i++) {
+    const float *r = rays6 + 6 * i;
+    out[i] = node_touched(nd.bmin, nd.bmax, nd.child, r[0], r[1], r[2], r[3], r[4], r[5], t_min, t_max) ? 1 : 0;
+  }
   return CRT_OK;
 }
 

@@ -159,6 +159,15 @@ int crt_scene_image_check(CrtScene *s, uint64_t out[8]);
  * a caller do the same. n_prims receives the record count; at most cap_prims records are copied to words16 (which may
  * be NULL when cap_prims is 0). */
 int crt_scene_image_prims(CrtScene *s, uint32_t *words16, size_t cap_prims, size_t *n_prims);
+/* Host-only (no GPU needed): the renderer's root cull as a function. For n rays of six floats each (origin, direction)
+ * touched[i] = 1 when ray i, on [t_min, t_max], touches the box of at least one child of the root node of the image this
+ * scene would upload, else 0 — the traversal's first node step (RaySlab::slab4, bvh.rs:790-808, with safe_inv3,
+ * bvh.rs:662-668), evaluated by the very function the renderer's generate kernel runs, compiled for the host. A ray with
+ * touched = 0 is a ray Bvh::hit reports as a miss after expanding the root alone; the per-stage renderer finishes such
+ * camera rays where they are generated, in frames that show enough background for that to pay (CRT_ROOT_CULL=0: never,
+ * 1: wherever the result allows it). *root receives the image's root node index,
+ * CRT_INVALID_ID for an empty scene (then every touched[i] = 0). */
+int crt_scene_root_touched_n(CrtScene *s, const float *rays6, size_t n, float t_min, float t_max, uint8_t *touched, uint32_t *root);
 /* Host-only (no GPU needed): which instance of the traversal engine this library selects for the image the scene would
  * upload — ONE function decides it for the renderer, the batched and the single-ray queries — verified against a census
  * of the image: the instance decodes every child word (the four-wave kernels carry no direct-leaf form) and keeps every
