@@ -369,6 +369,208 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
   if ((s.cold & kColdCubic) && (e.wide || !e.cubic || !(s.cold & kColdCurve))) return false;  // ... without the span's walk
   return ((int)(s.cold & (kColdAll | kColdCurve | kColdCubic)) & ~kernel_cold) == 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The renderer's launch plan: which kernel instances run one batch. plan_launches decides it once per batch from a
+// PlanInputs — every fact the choice depends on, as plain values — and names each instance by an InstanceKey;
+// kernels/pathtrace.hip holds the table {key, kernel pointer} built from the lists below and launches through what it
+// finds there. A new instance is one row of a list and one line of policy in plan_launches. Plain C++17, no HIP names:
+// tests/test_launch_plan.py sweeps the function on the CPU.
+// ---------------------------------------------------------------------------------------------
+enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC };
+struct InstanceKey {  // a kernel template and its arguments, in the template's order (bools as 0 / 1)
+  uint8_t family = KF_NONE;
+  uint8_t arg[5] = {0, 0, 0, 0, 0};
+  bool none() const { return family == KF_NONE; }
+  bool operator==(const InstanceKey &o) const {
+    return family == o.family && arg[0] == o.arg[0] && arg[1] == o.arg[1] && arg[2] == o.arg[2] && arg[3] == o.arg[3] && arg[4] == o.arg[4];
+  }
+};
+#define CRT_INSTANCE_KEY(family, kernel, ...) ::crt::InstanceKey{::crt::KF_##family, {__VA_ARGS__}}
+// Every instance of a multi-form kernel this build holds, one list per kernel signature: X(family, kernel, template
+// arguments...). The cold arguments are written as numbers: 2 = kColdNormal, 7 = kColdAll, 15 = kColdAll | kNoPackets,
+// 23 = kColdAll | kColdCurve, 55 = kColdAll | kColdCurve | kColdCubic.
+#if CRT_WIDE_DIRECT_BUILD  // the four-wave instances with the direct engine copy (WIDE = 2)
+#define CRT_WIDE_DIRECT_INSTANCES_EXTEND(X) X(EXTEND, k_extend, false, 2, 0) X(EXTEND, k_extend, false, 2, 2) X(EXTEND, k_extend, false, 2, 7)
+#define CRT_WIDE_DIRECT_INSTANCES_SHADOW(X) X(SHADOW, k_shadow, false, 2)
+#else
+#define CRT_WIDE_DIRECT_INSTANCES_EXTEND(X)
+#define CRT_WIDE_DIRECT_INSTANCES_SHADOW(X)
+#endif
+#if CRT_NOPK_BUILD  // the packet-free instances of the fused kernel exist only in builds that ask for them
+#define CRT_NOPK_INSTANCES_PATH(X) X(PATH, k_path, 1, false, 15, false) X(PATH, k_path, 1, true, 15, false) X(PATH, k_path, 2, false, 15, false) X(PATH, k_path, 2, true, 15, false)
+#else
+#define CRT_NOPK_INSTANCES_PATH(X)
+#endif
+#define CRT_INSTANCES_EXTEND(X) /* k_extend<STATS, WIDE, COLD> */ \
+  X(EXTEND, k_extend, false, 0, 0) X(EXTEND, k_extend, false, 0, 2) X(EXTEND, k_extend, false, 0, 7) \
+  X(EXTEND, k_extend, false, 1, 0) X(EXTEND, k_extend, false, 1, 2) X(EXTEND, k_extend, false, 1, 7) \
+  CRT_WIDE_DIRECT_INSTANCES_EXTEND(X) \
+  X(EXTEND, k_extend, true, 0, 7) X(EXTEND, k_extend, true, 1, 7) \
+  X(EXTEND, k_extend, false, 0, 23) X(EXTEND, k_extend, true, 0, 23) X(EXTEND, k_extend, false, 0, 55) X(EXTEND, k_extend, true, 0, 55)
+#define CRT_INSTANCES_PATH(X) /* k_path<MATS, LIT, COLD, DRV>: simple-material tables (derived records or raw), then general ones */ \
+  X(PATH, k_path, 0, false, 0, true) X(PATH, k_path, 0, false, 7, true) X(PATH, k_path, 0, true, 0, true) X(PATH, k_path, 0, true, 7, true) \
+  X(PATH, k_path, 0, false, 0, false) X(PATH, k_path, 0, false, 7, false) X(PATH, k_path, 0, true, 0, false) X(PATH, k_path, 0, true, 7, false) \
+  X(PATH, k_path, 1, false, 7, false) X(PATH, k_path, 1, false, 23, false) X(PATH, k_path, 1, false, 55, false) \
+  X(PATH, k_path, 1, true, 7, false) X(PATH, k_path, 1, true, 23, false) X(PATH, k_path, 1, true, 55, false) \
+  X(PATH, k_path, 2, false, 7, false) X(PATH, k_path, 2, false, 23, false) X(PATH, k_path, 2, false, 55, false) \
+  X(PATH, k_path, 2, true, 7, false) X(PATH, k_path, 2, true, 23, false) X(PATH, k_path, 2, true, 55, false) \
+  CRT_NOPK_INSTANCES_PATH(X)
+#define CRT_INSTANCES_SHADE(X) /* k_shade<MATS, INF, WIDE, LIT, DRV>, k_shade_env<MATS, DRV> */ \
+  X(SHADE, k_shade, 0, false, false, false, true) X(SHADE, k_shade, 0, false, false, true, true) X(SHADE, k_shade, 0, false, true, false, true) \
+  X(SHADE, k_shade, 0, false, true, true, true) X(SHADE, k_shade, 0, true, false, true, true) \
+  X(SHADE, k_shade, 0, false, false, false, false) X(SHADE, k_shade, 0, false, false, true, false) X(SHADE, k_shade, 0, false, true, false, false) \
+  X(SHADE, k_shade, 0, false, true, true, false) X(SHADE, k_shade, 0, true, false, true, false) \
+  X(SHADE, k_shade, 1, false, false, false, false) X(SHADE, k_shade, 1, false, false, true, false) X(SHADE, k_shade, 1, true, false, true, false) \
+  X(SHADE, k_shade, 2, false, false, false, false) X(SHADE, k_shade, 2, false, false, true, false) X(SHADE, k_shade, 2, true, false, true, false) \
+  X(SHADE_ENV, k_shade_env, 0, true) X(SHADE_ENV, k_shade_env, 0, false) X(SHADE_ENV, k_shade_env, 1, false) X(SHADE_ENV, k_shade_env, 2, false)
+#define CRT_INSTANCES_SHADE_PIPE(X) /* k_shade_pipe<DRV> */ \
+  X(SHADE_PIPE, k_shade_pipe, true) X(SHADE_PIPE, k_shade_pipe, false)
+#define CRT_INSTANCES_SHADOW(X) /* k_shadow<STATS, WIDE>, k_shadow_curve<STATS>, k_shadow_cubic<STATS> */ \
+  X(SHADOW, k_shadow, false, 0) X(SHADOW, k_shadow, false, 1) CRT_WIDE_DIRECT_INSTANCES_SHADOW(X) X(SHADOW, k_shadow, true, 0) X(SHADOW, k_shadow, true, 1) \
+  X(SHADOW_CURVE, k_shadow_curve, false) X(SHADOW_CURVE, k_shadow_curve, true) X(SHADOW_CUBIC, k_shadow_cubic, false) X(SHADOW_CUBIC, k_shadow_cubic, true)
+
+// What the choice of a batch's kernels depends on. The renderer keeps one: the engine choice, the A/B knobs and the
+// build's switches are filled when it is created; what its Params hold, and the per-batch fields, before every plan.
+struct PlanInputs {
+  EngineSelect engine;     // which traversal-engine instance runs the image (select_engine)
+  DevScene scene{};        // read: root, direct_leaves, n_packets, cold
+  int mats_kind = 1;       // 0 simple / 1 general / 2 general with interior media: which instance of the shading code runs
+  bool mat_derived = true; // CRT_MAT_DERIVED: simple-material tables launch the instances that read the derived records
+  uint32_t n_lights = 0;
+  bool has_inf_lights = false, has_env = false;  // a light at infinity; a mapped dome among them
+  uint32_t strategy = 0;   // CRT_STRATEGY_*
+  bool has_motion = false, lens = false;         // a moving instance; lens radius > 0
+  bool mat_index = false;  // the material table is deduplicated (Params::mat_index)
+  uint32_t partition = 0, class_stats = 0, n_materials = 0, max_depth = 0;
+  // Two pipelines: FUSED — the whole path loop of a batch in one launch (k_path, three workgroups per CU) — and PER-STAGE
+  // with the traversal kernels select_engine names. Every scene prefers one launch per stage for large batches: the
+  // lanes then overlap launches of different stages and bounces, which one fused launch per lane cannot; the 2-3
+  // launches per bounce cost ~0.8 ms per batch, worth it from `stage_min_paths` paths up (cornellbox 1080p, fused /
+  // per-stage Mray/s: 66 M paths 7507 / 7300, 133 M 7658 / 7900). CRT_FUSED / CRT_PREFER_STAGE / CRT_STAGE_MIN_PATHS override.
+  int force_fused = -1;
+  bool prefer_stage = true;
+  size_t stage_min_paths = (size_t)96 << 20;
+  int tail_from = 12;             // CRT_TAIL_FROM: the bounce from which a per-stage batch finishes in one fused launch (0: never)
+  int noclassify_from = 1 << 30;  // CRT_NOCLASSIFY_FROM: per-stage shade without its CLASSIFY pass from this bounce on
+  int shade_wide = -1;            // CRT_SHADE_WIDE: 0 = the three-wave shade kernels even beside four-wave traversal kernels (A/B)
+  int shade_pipe = 1;             // CRT_SHADE_PIPE: 0 = never the pipelined four-wave shade kernel (A/B, tests)
+  bool cam_compact_ok = true;     // CRT_CAM_COMPACT
+  int root_cull_knob = -1;        // CRT_ROOT_CULL: 0 = generate never finishes a camera ray, 1 = wherever the rule allows (A/B, tests)
+  float root_miss_share = 0.0f;   // share of a coarse grid of camera rays that misses every child of the root (pathtrace.hip)
+  // per batch
+  size_t total = 0;               // paths of the batch
+  bool stats = false;             // the stats build (crt_render_samples_stats)
+  // the build's switches that gate forms (kernels/pathtrace.hip)
+  bool cam_compact_build = true, wide_direct_build = CRT_WIDE_DIRECT_BUILD != 0, nopk_build = CRT_NOPK_BUILD != 0;
+  bool shade_pipe_build = true, root_cull_build = true;
+  int pipe_mat_max = 0;
+};
+// The root cull pays where at least an eighth of the frame shows background: between the share that lost and the shares
+// that won (profiles/README.md — cornellbox, 0.44 of its camera rays culled, +1.7 %; openpbr_showcase, 0.23, +1 %;
+// veach_mis, 0.06, and the two scenes that fill their frame lose 1-3 %).
+constexpr float kRootCullMinShare = 0.125f;
+// The pipelined shade kernel serves unlit simple-material scenes of one material class whose whole material table fits
+// the arena beside the staging blocks (pipe_mat_max); every other scene keeps k_shade with its LDS-resident table.
+inline bool shade_pipe_fits(const PlanInputs &q) {
+  return q.shade_pipe_build && q.shade_pipe != 0 && q.mats_kind == 0 && q.n_lights == 0 && !q.has_motion && !q.mat_index &&
+         q.partition == 0 && !q.class_stats && q.n_materials <= (uint32_t)q.pipe_mat_max;
+}
+struct LaunchPlan {
+  bool fused = true;              // one k_path launch for the whole path loop; otherwise one launch per stage and bounce
+  bool wide = false;              // per-stage: the four-wave traversal kernels
+  uint32_t tail_at = 0xffffffffu; // per-stage: the bounce from which k_path finishes the batch (0xffffffff: never)
+  uint32_t cam_compact = 0;       // Params::cam_compact: 0 / 1 = camera paths as 16-byte records / 2 = with plane d beside them
+  bool root_cull = false;         // generate finishes the camera rays that miss the root's boxes
+  bool shadow = false;            // the shadow stage runs: a light list and a strategy that samples it
+  int noclassify_from = 1 << 30;  // the bounce from which shade drops CLASSIFY
+  int ext_cold = 0, path_cold = 0;  // the cold arguments the closest-hit kernels were chosen for (the refusal's text)
+  InstanceKey path, extend, shade, shade_early, shadow_key;  // path: the fused launch or the tail; shade_early: the
+                                  // pipelined instance, which runs the bounces before noclassify_from; none = not launched
+  bool shade_piped() const { return !shade_early.none(); }
+};
+// The EngineSelect a traversal instance of width w amounts to on this image (0 = three waves, 1 = four, the flat engine
+// copy only, 2 = four, the direct copy only) — run_traversal picks the three-wave kernels' copy from the image.
+inline EngineSelect engine_of_width(const EngineSelect &e, const DevScene &s, int w) {
+  EngineSelect l = e;
+  l.wide = w != 0;
+  l.wide_direct = w == 2;
+  l.direct = w != 1 && CRT_DIRECT_LEAVES != 0 && s.direct_leaves != 0;
+  return l;
+}
+// CRT_OK and the plan, or CRT_ERR_UNSUPPORTED and a plan that names nothing: a launch the image cannot take is refused,
+// never made. engine_accepts is asked once per traversal-bearing instance the plan names, with the EngineSelect that
+// instance amounts to and its own cold argument.
+inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
+  const EngineSelect &e = q.engine;
+  LaunchPlan pl;
+  pl.fused = q.force_fused >= 0 ? q.force_fused != 0 : !(q.prefer_stage && q.total >= q.stage_min_paths);
+  // the stats build is the per-stage one; no fused instance carries the lights at infinity (see k_path) — nor a tail then
+  if (q.stats || q.has_inf_lights) pl.fused = false;
+  const bool stage = !pl.fused, lit = q.n_lights > 0;
+  pl.wide = stage && e.wide;  // the fused kernel is a three-wave kernel whatever the scene prefers
+  // The TAIL: from bounce `tail_from` on, what is left of the batch — roulette has ended all but a few paths per ten
+  // thousand by then (bench: 6.6 M of 531 M rays at bounce 4, 0.1 M at bounce 6) — runs as ONE launch of the fused
+  // path-loop kernel over the same segments instead of two or three launches per bounce up to the depth limit (bench,
+  // depth 32: 52 launches, ~2 ms of a 137 ms step). Not for the stats build: its kernels count.
+  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights;
+  if (tail) pl.tail_at = (uint32_t)q.tail_from;
+  // camera paths as 16-byte records: per-stage launches of an UNLIT scene, pinhole camera, static scene
+  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion) ? 1u : 0u;
+  // The root cull (generate_segment_cull): per-stage launches of an image whose root is a node, when a camera ray that
+  // escapes ends on the sky gradient — a depth limit above 0 and no light at infinity (their escaped rays take the
+  // vertex step) — and where the frame shows enough background for it to pay (CRT_ROOT_CULL=1 skips that estimate). Not
+  // in the stats build: its kernels count the node visits the oracle counts. Lens cameras, moving instances, adaptive
+  // stopping and curve images qualify: the root step depends on none of them. The compact form then carries plane d
+  // (cam_compact == 2) where the shade instances hold that form: simple-material tables. The general instances sit at
+  // their register limit (k_shade<2, false, false, false, false> gained three spilled registers with it) and read the
+  // full form instead.
+  pl.root_cull = q.root_cull_build && q.root_cull_knob != 0 && (q.root_cull_knob > 0 || q.root_miss_share >= kRootCullMinShare) &&
+                 stage && !q.stats && q.scene.root != CRT_INVALID_ID && q.max_depth > 0 && !q.has_inf_lights;
+  if (pl.root_cull && pl.cam_compact) pl.cam_compact = q.mats_kind == 0 ? 2u : 0u;
+  pl.shadow = stage && lit && q.strategy != CRT_STRATEGY_BSDF;
+  pl.noclassify_from = q.noclassify_from;
+  // The cold per-ray state the image can need (DevScene::cold) picks the closest-hit kernels' instance: none / the
+  // pending normal only / everything for k_extend, none / everything for the k_path of simple-material tables; general
+  // tables run the full-cold k_path, or its packet-free instance; a curve image one instance each: everything + the
+  // arm(s). The stats build counts on the full-cold instances.
+  const int curve_cold = e.curve ? (int)kColdAll | e.curve_cold() : 0;
+  const bool simple = q.mats_kind == 0, drv = simple && q.mat_derived;
+  pl.ext_cold = e.curve ? curve_cold : (q.stats ? (int)kColdAll : e.ext_cold);
+  pl.path_cold = e.curve ? curve_cold : (simple ? (e.path_cold & (int)kColdAll) : (int)kColdAll | (q.nopk_build ? e.path_cold & (int)kNoPackets : 0));
+  auto key = [](KernelFamily f, int a0, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0) {
+    InstanceKey k;
+    k.family = f;
+    k.arg[0] = (uint8_t)a0; k.arg[1] = (uint8_t)a1; k.arg[2] = (uint8_t)a2; k.arg[3] = (uint8_t)a3; k.arg[4] = (uint8_t)a4;
+    return k;
+  };
+  // the per-stage traversal kernels' width: curve images run three-wave instances only, and the stats build of a
+  // direct-leaf image counts on them too (the counters do not depend on the engine split)
+  const bool wdirect = pl.wide && e.wide_direct && q.wide_direct_build;
+  const int width = e.curve ? 0 : (wdirect ? (q.stats ? 0 : 2) : (pl.wide ? 1 : 0));
+  int shadow_cold = (int)kColdAll;  // an any-hit query keeps no cold state: k_shadow serves every image without curves
+  if (pl.fused || tail)  // simple-material tables: derived records or raw ones, cold none / everything
+    pl.path = key(KF_PATH, q.mats_kind, lit, simple && pl.path_cold != 0 ? (int)kColdAll : pl.path_cold, drv);
+  if (stage) {
+    pl.extend = key(KF_EXTEND, q.stats, width, pl.ext_cold);
+    // the shade instance: material table, lights at infinity, four waves (simple materials without lights at infinity,
+    // when the scene runs the wide kernels), whether the light list is empty; a mapped dome: the instances with its arm
+    const bool shade_wide = simple && !q.has_inf_lights && pl.wide && !q.mat_index && q.shade_wide != 0;
+    pl.shade = q.has_env ? key(KF_SHADE_ENV, q.mats_kind, drv) : key(KF_SHADE, q.mats_kind, q.has_inf_lights, shade_wide, lit, drv);
+    if (shade_wide && shade_pipe_fits(q) && q.noclassify_from > 0) pl.shade_early = key(KF_SHADE_PIPE, drv);
+    if (pl.shadow) {
+      if (e.curve) { pl.shadow_key = key(e.cubic ? KF_SHADOW_CUBIC : KF_SHADOW_CURVE, q.stats); shadow_cold = curve_cold; }
+      else pl.shadow_key = key(KF_SHADOW, q.stats, width);
+    }
+  }
+  const bool ok = (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
+                  (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
+                  (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
+  if (!ok) pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = InstanceKey{};
+  out = pl;
+  return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
+}
+
 // CRT_WIDE (A/B runs, tests): 1 asks for the four-wave kernels, 0 for the three-wave ones. A request the image cannot
 // take falls back to the scene's own preference — the knob sweeps whole test sets, direct-leaf scenes included.
 int wide_request();  // -1 unset

@@ -209,7 +209,7 @@ struct Params {
   uint32_t cam_compact;
   // Per-stage launches: generate finishes every camera ray that touches no child box of the root node on the spot — the
   // sky gradient into the staging film, the counters the miss step feeds — and appends only the others to its segment
-  // (generate_segment_cull). Set per batch by Renderer::render_lane, which holds the rule.
+  // (generate_segment_cull). Set per batch from the launch plan (crt_internal.h, plan_launches), which holds the rule.
   uint32_t root_cull;
   // The library's table of live environments (environment.cpp), read by the mapped-dome instances only (k_shade_env):
   // a CRT_LIGHT_DOME_MAP record names its environment by id. nullptr when the light list holds no such record.
@@ -429,7 +429,7 @@ __device__ __forceinline__ size_t camera_slot_sample(size_t k) {
 // ensure_buffers). D = plane d's words as generate would have written them — under the root cull (cam_compact == 2) the
 // words generate DID write: the caller has read plane d into D, the slot of a compacted survivor says nothing. PLANE_D:
 // the instance holds that form (the simple-material shade kernels; the general ones are at their register limit and
-// run the full form under the root cull instead — Renderer::render_lane).
+// run the full form under the root cull instead — plan_launches).
 template <bool PLANE_D>
 __device__ __forceinline__ void compact_camera_path(const Params &P, uint32_t k, float4 a, float4 &A, float4 &B, uint4 &D) {
   const V3 o = ld3(P.camera.origin) + splat(0.0f);
@@ -495,7 +495,7 @@ __device__ __forceinline__ void generate_segment(const Params &P, const PathSoA 
     if (blockIdx.x == 0) atomicAdd(&C->stats[0], (unsigned long long)total);  // camera_rays (tracer.rs:585)
   }
 }
-// ---- generate with the ROOT CULL (per-stage launches only; Renderer::render_lane holds the rule) ----
+// ---- generate with the ROOT CULL (per-stage launches only; plan_launches holds the rule) ----
 // On an open frame nearly every camera ray that escapes does so at the root: it tests the root's four child boxes,
 // touches none and leaves (cornellbox 1080p: 44 % of the camera rays; 16 of 20 736 escaping rays get past the root). Such
 // a ray used to be written here, fetched, set up and stepped once by the first extend, classified, queued and finished by
@@ -1147,7 +1147,7 @@ constexpr int kPipeWaveDwords = kPipePlanes * 256 + 64;
 constexpr int kPipeStageDwords = (kBlock / 64) * kPipeWaveDwords;
 constexpr int kPipeRingDwords = 2 * (int)kPipeRing;
 constexpr int kMatDwords = (int)(sizeof(CrtMaterial) / 4);
-// The rule the host applies (Renderer::shade_pipe_fits): the pipelined instance runs only where the WHOLE material table
+// The rule the host applies (crt_internal.h, shade_pipe_fits): the pipelined instance runs only where the WHOLE material table
 // fits beside its staging blocks; every other scene keeps k_shade and its LDS-resident table. (A lit scene's plane e would
 // add 4 KB of staging and a partitioned scene's four rings 4 KB of rings: neither leaves room for a table.)
 constexpr int kPipeMatMax = (kArenaWide - kSobolLdsWords - kPipeRingDwords - kPipeStageDwords) / kMatDwords;
@@ -1604,6 +1604,37 @@ __global__ __launch_bounds__(kBlock) void k_film_out(const float4 *film, uint32_
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
+// The instance table: every instance of the multi-form kernels this build holds, named once — the lists of
+// crt_internal.h expanded to rows {key, kernel}, one typed pointer per kernel signature. A launch plan names keys
+// (plan_launches); a key without a row is an error, never another instance.
+// ---------------------------------------------------------------------------------------------
+using ExtendFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, CrtTravStats *);
+using PathFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, float4 *, uint32_t, uint32_t, uint32_t, int);
+using ShadeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int);
+using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int);
+using ShadowFn = void (*)(Params, PathSoA, ShadowSoA, Counters *, float4 *, CrtTravStats *);
+template <class Fn>
+struct InstanceRow { InstanceKey key; Fn fn; };
+#define CRT_ROW(family, kernel, ...) {CRT_INSTANCE_KEY(family, kernel, __VA_ARGS__), kernel<__VA_ARGS__>},
+static const InstanceRow<ExtendFn> kExtendRows[] = {CRT_INSTANCES_EXTEND(CRT_ROW)};
+static const InstanceRow<PathFn> kPathRows[] = {CRT_INSTANCES_PATH(CRT_ROW)};
+static const InstanceRow<ShadeFn> kShadeRows[] = {CRT_INSTANCES_SHADE(CRT_ROW)};
+static const InstanceRow<ShadePipeFn> kShadePipeRows[] = {CRT_INSTANCES_SHADE_PIPE(CRT_ROW)};
+static const InstanceRow<ShadowFn> kShadowRows[] = {CRT_INSTANCES_SHADOW(CRT_ROW)};
+#undef CRT_ROW
+// The kernel a key names (nullptr for the empty key: nothing to launch); false when the build holds no such instance.
+template <class Fn, size_t N>
+static bool find_instance(const InstanceRow<Fn> (&rows)[N], const InstanceKey &key, Fn &fn) {
+  fn = nullptr;
+  if (key.none()) return true;
+  for (const InstanceRow<Fn> &r : rows)
+    if (r.key == key) { fn = r.fn; return true; }
+  set_error_text("render refused: no such instance in this build (family %d: %d, %d, %d, %d, %d)", (int)key.family, (int)key.arg[0],
+                 (int)key.arg[1], (int)key.arg[2], (int)key.arg[3], (int)key.arg[4]);
+  return false;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host side: Renderer (tracer.rs:137-148) over the kernels above
 // ---------------------------------------------------------------------------------------------
 struct Renderer {
@@ -1637,41 +1668,27 @@ struct Renderer {
   float4 *film = nullptr;
   CrtMaterial *d_materials = nullptr;
   DevMaterial *d_mat_derived = nullptr;  // one per record of d_materials (k_derive_materials)
-  bool mat_derived = true;         // CRT_MAT_DERIVED: simple-material scenes launch the instances that read it
   uint8_t *d_mat_class = nullptr;  // material_class() per record of d_materials
   uint16_t *d_mat_index = nullptr; // geom_id -> record, when the table is deduplicated (Params::mat_index)
   DevMedium *d_media = nullptr;  // [n_materials] by geom_id, then [n_materials] by compact id
   bool has_media = false;
-  int mats_kind = 1;  // 0 simple / 1 general / 2 general with interior media: which instance of the shading code runs
   // adaptive stopping (variance_threshold > 0): per-pixel luminance statistics, sample counts and the active list
   PixelStats *d_pstats = nullptr;
   uint32_t *d_state = nullptr, *d_active = nullptr, *d_count = nullptr;
   uint32_t n_act = 0, min_spp = 2;
   float variance_threshold = 0.0f;
-  // Two pipelines: FUSED — the whole path loop of a batch in one launch (k_path, three workgroups per CU) — and PER-STAGE
-  // with the WIDE traversal kernels (four workgroups per CU). The scene decides which one it prefers (crt_renderer_new:
-  // `wide`), the batch whether the per-stage form pays: its 2-3 launches per bounce cost ~0.8 ms per batch, worth it from
-  // `stage_min_paths` paths up. CRT_FUSED / CRT_WIDE / CRT_STAGE_MIN_PATHS override (A/B, per-stage timing, tests).
-  EngineSelect engine;     // which traversal-engine instance runs this scene's image (crt_internal.h, select_engine)
-  bool wide = false;       // = engine.wide: per-stage launches run the four-wave traversal kernels
-  // The scene prefers one launch per stage for large batches — since round 4 every scene does: the lanes then overlap
-  // launches of different stages and bounces, which one fused launch per lane cannot (measured first on the three-wave
-  // kernels, 1080p / 4K, Mray/s fused -> per-stage: stress 2460 -> 2559, PointInstancedMedCity 2191 -> 2224, the
-  // 7 M-triangle synthetic scene 3307 -> 3400; the per-stage traversal kernels are the four-wave instances select_engine
-  // names — flat engine copy or, for direct-leaf images, the direct one; profiles/README.md).
-  bool prefer_stage = false;
-  bool cam_compact_ok = true;  // CRT_CAM_COMPACT
-  int root_cull_knob = -1;     // CRT_ROOT_CULL: 0 = generate never finishes a camera ray, 1 = wherever the rule allows (A/B, tests)
-  // What the cull can save grows with the share of the frame that shows background; what it costs does not: generate's
-  // slab tests and compaction, plane d beside the compact form (measured: profiles/README.md — cornellbox, 0.44 of its
-  // camera rays culled, +1.7 %; openpbr_showcase, 0.23, +1 %; veach_mis, 0.06, and the two scenes that fill their frame
-  // lose 1-3 %). So the renderer looks first: the root step of the pixel-centre rays of a 32 x 18 grid over the frame,
-  // through the lens centre, on the host (root_miss_share, at creation), and culls only where at least an eighth of them
-  // miss every child of the root — between the share that lost and the shares that won.
-  float root_miss_share = 0.0f;
-  static constexpr float kRootCullMinShare = 0.125f;
+  // Which kernel instances run a batch: plan_launches (crt_internal.h) decides from `in` — the image's engine choice
+  // (select_engine), the tables, the A/B knobs and this build's switches, filled at creation; the batch's path count and
+  // whether it is the stats build, set per batch — and render_lane launches what the instance table below holds for the
+  // plan's keys. last_plan: what the LAST batch ran (crt_renderer_pipeline); until the first, the scene's preference.
+  PlanInputs in;
+  LaunchPlan last_plan;
+  // What the root cull can save grows with the share of the frame that shows background; what it costs does not:
+  // generate's slab tests and compaction, plane d beside the compact form. So the renderer looks first: the root step of
+  // the pixel-centre rays of a 32 x 18 grid over the frame, through the lens centre, on the host (at creation), and
+  // plan_launches culls only where at least kRootCullMinShare of them miss every child of the root.
   void estimate_root_miss_share() {
-    root_miss_share = 0.0f;
+    in.root_miss_share = 0.0f;
     if (!scene || scene->bvh.wide.empty()) return;
     const WideNode &nd = scene->bvh.wide[0];  // the committed tree's root (bvh.rs:442-447): the image's root node, child words apart
     uint32_t child[4];
@@ -1686,24 +1703,9 @@ struct Renderer {
         for (int a = 0; a < 3; a++) d[a] = c.lower_left[a] + c.horizontal[a] * sx + c.vertical[a] * sy - c.origin[a];
         if (!node_touched(nd.bmin, nd.bmax, child, c.origin[0], c.origin[1], c.origin[2], d[0], d[1], d[2], 0.001f, CRT_INF)) missed++;
       }
-    root_miss_share = (float)missed / (float)(GW * GH);
+    in.root_miss_share = (float)missed / (float)(GW * GH);
   }
-  bool root_culled = false;    // the LAST batch's generate launches ran the root cull (crt_renderer_pipeline)
-  int shade_wide = -1;            // CRT_SHADE_WIDE: 0 = the three-wave shade kernels even beside four-wave traversal kernels (A/B)
   size_t max_batch_slots = 0;     // CRT_MAX_BATCH_SLOTS (tests): ensure_buffers fails above this many slots; 0 = no limit
-  int tail_from = 12;             // CRT_TAIL_FROM: the bounce from which a per-stage batch finishes in one fused launch
-  int noclassify_from = 1 << 30;  // CRT_NOCLASSIFY_FROM: per-stage shade without its CLASSIFY pass from this bounce on
-  int shade_pipe = 1;             // CRT_SHADE_PIPE: 0 = never the pipelined four-wave shade kernel (A/B, tests)
-  bool shade_piped = false;       // the LAST batch ran it (crt_renderer_pipeline)
-  // The pipelined shade kernel serves unlit simple-material scenes of one material class whose whole material table fits
-  // the arena beside the staging blocks (kPipeMatMax); every other scene keeps k_shade with its LDS-resident table.
-  bool shade_pipe_fits() const {
-    return kShadePipeBuild && shade_pipe != 0 && mats_kind == 0 && P.n_lights == 0 && !P.has_motion && !P.mat_index &&
-           P.partition == 0 && !P.class_stats && P.n_materials <= (uint32_t)kPipeMatMax;
-  }
-  int force_fused = -1;    // CRT_FUSED: -1 unset
-  size_t stage_min_paths = (size_t)96 << 20;  // cornellbox 1080p, fused / per-stage Mray/s: 66 M paths 7507 / 7300, 133 M 7658 / 7900
-  bool fused = true;       // what the LAST batch ran (crt_renderer_pipeline)
   int cus = 256, fused_mult = 3, stage_mult = 8, mult_forced = 0;
   CrtLight *d_lights = nullptr;
   std::vector<std::shared_ptr<void>> environments;  // what the mapped domes of the light list name (Params::envs is set iff any)
@@ -1859,7 +1861,7 @@ struct Renderer {
     // every lane's buffers BEFORE any launch: an allocation that fails then fails with nothing of this batch in flight
     for (int l = 0; l < L; l++) {
       Params scratch = P;
-      const int rc = plan_lane(lanes[l], scratch, count[l], nullptr);
+      const int rc = plan_lane(lanes[l], scratch, count[l], false);
       if (rc != CRT_OK) return rc;
     }
     // every lane starts behind what the caller's stream has queued (the previous batch's film fold reads the staging
@@ -1889,15 +1891,29 @@ struct Renderer {
     return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : fail(CRT_ERR_NO_DEVICE);
   }
 
-  // Pipeline, grid and segment size of one lane's batch of n_samples, and its buffers (they grow when a batch needs
-  // more slots than any before). Sets fused / grid for the launches that follow and p.seg_cap.
-  int plan_lane(Lane &B, Params &p, uint32_t n_samples, CrtTravStats *d_tstats) {
+  // The launch plan of one lane's batch of n_samples (crt_internal.h, plan_launches), its grid and segment size, and its
+  // buffers (they grow when a batch needs more slots than any before). Sets last_plan / grid for the launches that
+  // follow, and p.seg_cap, p.cam_compact, p.root_cull.
+  int plan_lane(Lane &B, Params &p, uint32_t n_samples, bool stats) {
     const size_t total = (size_t)p.n_act * n_samples;
-    fused = force_fused >= 0 ? force_fused != 0 : !(prefer_stage && total >= stage_min_paths);
-    if (d_tstats) fused = false;  // the stats build is the per-stage one
-    if (P.has_inf_lights) fused = false;  // no fused instance for lights at infinity (see k_path)
-    grid = batch_grid(total, fused);
+    in.total = total;
+    in.stats = stats;
+    // from P at every plan, so that nothing set after creation leaves the plan stale; the engine choice, mats_kind and
+    // the root's miss share are derived at creation from what no entry point changes (the image, the table, the camera)
+    in.scene = P.scene;
+    in.n_lights = P.n_lights; in.has_inf_lights = P.has_inf_lights != 0; in.has_env = P.envs != nullptr; in.strategy = P.strategy;
+    in.has_motion = P.has_motion != 0; in.lens = P.camera.lens_radius > 0.0f;
+    in.mat_index = P.mat_index != nullptr; in.partition = P.partition; in.n_materials = P.n_materials; in.max_depth = P.max_depth;
+    in.class_stats = P.class_stats;
+    if (plan_launches(in, last_plan) != CRT_OK) {
+      set_error_text("render refused: the selected kernels (wide %d, cold %d / %d) cannot run this image (direct words %u, cold %u)",
+                     (int)last_plan.wide, last_plan.ext_cold, last_plan.path_cold, P.scene.direct_leaves, P.scene.cold);
+      return CRT_ERR_UNSUPPORTED;
+    }
+    grid = batch_grid(total, last_plan.fused);
     p.seg_cap = (uint32_t)(((total + (size_t)grid * kBlock - 1) / ((size_t)grid * kBlock)) * kBlock);
+    p.cam_compact = last_plan.cam_compact;
+    p.root_cull = last_plan.root_cull ? 1u : 0u;
     return ensure_buffers(B, (size_t)p.seg_cap * grid);  // >= total: the staging film's (sample, active pixel) slots too
   }
 
@@ -1912,25 +1928,18 @@ struct Renderer {
     p.sample_begin = sample_begin;
     p.n_act = adaptive ? n_act : P.n_pix;
     p.active = (adaptive && n_act < P.n_pix) ? d_active : nullptr;
-    if (const int rc = plan_lane(B, p, n_samples, d_tstats)) return rc;
-    shade_piped = false;
+    if (const int rc = plan_lane(B, p, n_samples, d_tstats != nullptr)) return rc;
+    const LaunchPlan plan = last_plan;
+    PathFn path;
+    ExtendFn extend;
+    ShadeFn shade;
+    ShadePipeFn shade_pipe;
+    ShadowFn shadow;
+    if (!find_instance(kPathRows, plan.path, path) || !find_instance(kExtendRows, plan.extend, extend) ||
+        !find_instance(kShadeRows, plan.shade, shade) || !find_instance(kShadePipeRows, plan.shade_early, shade_pipe) ||
+        !find_instance(kShadowRows, plan.shadow_key, shadow))
+      return CRT_ERR_UNSUPPORTED;
     float4 *staging = B.staging;
-    const bool wide = !fused && this->wide;  // per-stage launches take the scene's preferred traversal kernels
-    const bool wdirect = wide && engine.wide_direct && CRT_WIDE_DIRECT_BUILD != 0;  // ... their direct-engine instances
-    // camera paths as 16-byte records: per-stage launches of an UNLIT scene, pinhole camera, static scene
-    // (CRT_CAM_COMPACT=0: A/B, tests)
-    p.cam_compact = (CRT_CAM_COMPACT_BUILD && !fused && cam_compact_ok && P.n_lights == 0 && !(P.camera.lens_radius > 0.0f) && !P.has_motion) ? 1u : 0u;
-    // The root cull (generate_segment_cull): per-stage launches of an image whose root is a node, when a camera ray that
-    // escapes ends on the sky gradient — a depth limit above 0 and no light at infinity (their escaped rays take the
-    // vertex step) — and where the frame shows enough background for it to pay (root_miss_share; CRT_ROOT_CULL=1 skips
-    // that estimate). Not in the stats build: its kernels count the node visits the oracle counts. Lens cameras, moving
-    // instances, adaptive stopping and curve images qualify: the root step depends on none of them. The compact form
-    // then carries plane d (cam_compact == 2) where the shade instances hold that form: simple-material tables. The
-    // general instances sit at their register limit (k_shade<2, false, false, false, false> gained three spilled
-    // registers with it) and read the full form instead.
-    root_culled = kRootCullBuild && root_cull_knob != 0 && (root_cull_knob > 0 || root_miss_share >= kRootCullMinShare) && !fused && !d_tstats && P.scene.root != kInvalid && P.max_depth > 0 && !P.has_inf_lights;
-    p.root_cull = root_culled ? 1u : 0u;
-    if (root_culled && p.cam_compact) p.cam_compact = mats_kind == 0 ? 2u : 0u;
     // the film fold: plain sum, or with the luminance statistics and the stopping rule, then the new active list
     auto fold = [&]() -> int {
       if (!fold_here) return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : CRT_ERR_NO_DEVICE;  // the caller folds the lanes in order
@@ -1950,163 +1959,25 @@ struct Renderer {
       n_act = h;
       return CRT_OK;
     };
-    const bool lit = P.n_lights > 0;  // the kernel instance; whether the strategy samples the lights is checked in shade
-    const bool drv = mats_kind == 0 && mat_derived;  // simple-material tables read the derived records (CRT_MAT_DERIVED=0: never)
-    // the cold per-ray state the scene can need (DevScene::cold) picks the closest-hit kernels' instance: none / the
-    // pending normal only / everything for the per-stage k_extend, none / everything for the fused kernel of simple
-    // scenes — decided by select_engine, with the image in hand; a launch the image cannot take is refused, never made
-    const bool curve = engine.curve;  // curve images: the three-wave instances with the rounded-cone arm, the general k_path
-    const bool cubic = engine.cubic;  // ... cubic images: their instances with the span's walk as well
-    const int ext_cold = curve ? (int)kColdAll | engine.curve_cold() : (d_tstats ? (int)kColdAll : engine.ext_cold);
-    // (general material tables run the full-cold fused kernel — or its packet-free instance, for images without a Tri4 packet)
-    const bool nopk = mats_kind != 0 && (engine.path_cold & (int)kNoPackets) != 0;
-    const int path_cold = curve ? (int)kColdAll | engine.curve_cold()
-                                : (mats_kind == 0 ? (engine.path_cold & (int)kColdAll) : (int)(kColdAll | (nopk ? kNoPackets : 0u)));
-    {
-      EngineSelect launched = engine;
-      launched.wide = wide;  // the fused kernel is a three-wave kernel whatever the scene prefers
-      launched.wide_direct = wide && engine.wide_direct;
-      launched.direct = (!wide || launched.wide_direct) && CRT_DIRECT_LEAVES != 0 && P.scene.direct_leaves != 0;  // run_traversal picks the copy from the image
-      const bool tail = !fused && tail_from > 0 && !d_tstats && !P.has_inf_lights;
-      if (!engine_accepts(launched, P.scene, fused ? path_cold : (tail ? (ext_cold & path_cold) : ext_cold))) {
-        set_error_text("render refused: the selected kernels (wide %d, cold %d / %d) cannot run this image (direct words %u, cold %u)",
-                       (int)wide, ext_cold, path_cold, P.scene.direct_leaves, P.scene.cold);
-        return CRT_ERR_UNSUPPORTED;
-      }
-    }
-    if (fused) {  // one launch for the whole path loop (class 0 of the profile), then the film fold
-      timed(0, st, [&] {
-#define CRT_PATH(M, L, CO) CRT_PATH_D(M, L, CO, false)
-#define CRT_PATH_D(M, L, CO, D) \
-  hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0)
-#if CRT_NOPK_BUILD  // the packet-free instances exist only in builds that ask for them (A/B: profiles/README.md, round 4)
-#define CRT_PATH_NP(M, L) do { if (cubic) CRT_PATH(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else if (nopk) CRT_PATH(M, L, kColdAll | kNoPackets); else CRT_PATH(M, L, kColdAll); } while (0)
-#else
-#define CRT_PATH_NP(M, L) do { if (cubic) CRT_PATH(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_PATH(M, L, kColdAll | kColdCurve); else CRT_PATH(M, L, kColdAll); } while (0)
-#endif
-        switch (mats_kind * 2 + (lit ? 1 : 0)) {
-          // simple-material tables: the instances that read the derived records (drv), or the raw ones (CRT_MAT_DERIVED=0)
-          case 0:
-            if (drv) { if (path_cold == 0) CRT_PATH_D(0, false, 0, true); else CRT_PATH_D(0, false, kColdAll, true); }
-            else { if (path_cold == 0) CRT_PATH(0, false, 0); else CRT_PATH(0, false, kColdAll); }
-            break;
-          case 1:
-            if (drv) { if (path_cold == 0) CRT_PATH_D(0, true, 0, true); else CRT_PATH_D(0, true, kColdAll, true); }
-            else { if (path_cold == 0) CRT_PATH(0, true, 0); else CRT_PATH(0, true, kColdAll); }
-            break;
-          case 2: CRT_PATH_NP(1, false); break;
-          case 3: CRT_PATH_NP(1, true); break;
-          case 4: CRT_PATH_NP(2, false); break;
-          default: CRT_PATH_NP(2, true); break;
-        }
-#undef CRT_PATH_NP
-#undef CRT_PATH_D
-#undef CRT_PATH
-      });
+    if (plan.fused) {  // one launch for the whole path loop (class 0 of the profile), then the film fold
+      timed(0, st, [&] { hipLaunchKernelGGL(path, dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0); });
       return fold();
     }
     timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples, staging); });
     int cur = 0;
-    // The TAIL: from bounce `tail_from` on, what is left of the batch — roulette has ended all but a few paths per ten
-    // thousand by then (bench: 6.6 M of 531 M rays at bounce 4, 0.1 M at bounce 6) — runs as ONE launch of the fused
-    // path-loop kernel over the same segments instead of two or three launches per bounce up to the depth limit (bench,
-    // depth 32: 52 launches, ~2 ms of a 137 ms step). Not for the stats build (its kernels count) nor for lights at
-    // infinity (no fused instance). CRT_TAIL_FROM=n moves it (0: never).
-    const uint32_t tail_at = (tail_from > 0 && !d_tstats && !P.has_inf_lights) ? (uint32_t)tail_from : 0xffffffffu;
     for (uint32_t it = 0; it <= P.max_depth; it++) {
-      if (it >= tail_at) {
-        timed(3, st, [&] {
-#define CRT_TAIL(M, L, CO) CRT_TAIL_D(M, L, CO, false)
-#define CRT_TAIL_D(M, L, CO, D) \
-  hipLaunchKernelGGL((k_path<M, L, CO, D>), dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, it, cur)
-#if CRT_NOPK_BUILD
-#define CRT_TAIL_NP(M, L) do { if (cubic) CRT_TAIL(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else if (nopk) CRT_TAIL(M, L, kColdAll | kNoPackets); else CRT_TAIL(M, L, kColdAll); } while (0)
-#else
-#define CRT_TAIL_NP(M, L) do { if (cubic) CRT_TAIL(M, L, kColdAll | kColdCurve | kColdCubic); else if (curve) CRT_TAIL(M, L, kColdAll | kColdCurve); else CRT_TAIL(M, L, kColdAll); } while (0)
-#endif
-          switch (mats_kind * 2 + (lit ? 1 : 0)) {
-            case 0:
-              if (drv) { if (path_cold == 0) CRT_TAIL_D(0, false, 0, true); else CRT_TAIL_D(0, false, kColdAll, true); }
-              else { if (path_cold == 0) CRT_TAIL(0, false, 0); else CRT_TAIL(0, false, kColdAll); }
-              break;
-            case 1:
-              if (drv) { if (path_cold == 0) CRT_TAIL_D(0, true, 0, true); else CRT_TAIL_D(0, true, kColdAll, true); }
-              else { if (path_cold == 0) CRT_TAIL(0, true, 0); else CRT_TAIL(0, true, kColdAll); }
-              break;
-            case 2: CRT_TAIL_NP(1, false); break;
-            case 3: CRT_TAIL_NP(1, true); break;
-            case 4: CRT_TAIL_NP(2, false); break;
-            default: CRT_TAIL_NP(2, true); break;
-          }
-#undef CRT_TAIL_NP
-#undef CRT_TAIL_D
-#undef CRT_TAIL
-        });
+      if (it >= plan.tail_at) {  // the tail: what is left of the batch in one launch of the path-loop kernel
+        timed(3, st, [&] { hipLaunchKernelGGL(path, dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, it, cur); });
         break;
       }
-#define CRT_EXTEND(ST, W, CO) \
-  timed(0, st, [&] { hipLaunchKernelGGL((k_extend<ST, W, CO>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, it == 0 ? 1 : 0, d_tstats); })
-      // (the stats build of a direct-leaf image counts on the three-wave kernels: the counters do not depend on the engine split)
-      if (cubic) { if (d_tstats) CRT_EXTEND(true, 0, kColdAll | kColdCurve | kColdCubic); else CRT_EXTEND(false, 0, kColdAll | kColdCurve | kColdCubic); }  // never wide
-      else if (curve) { if (d_tstats) CRT_EXTEND(true, 0, kColdAll | kColdCurve); else CRT_EXTEND(false, 0, kColdAll | kColdCurve); }  // never wide
-      else if (d_tstats) { if (wide && !wdirect) CRT_EXTEND(true, 1, kColdAll); else CRT_EXTEND(true, 0, kColdAll); }
-#if CRT_WIDE_DIRECT_BUILD
-      else if (wdirect) { if (ext_cold == 0) CRT_EXTEND(false, 2, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 2, kColdNormal); else CRT_EXTEND(false, 2, kColdAll); }
-#endif
-      else if (wide) { if (ext_cold == 0) CRT_EXTEND(false, 1, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 1, kColdNormal); else CRT_EXTEND(false, 1, kColdAll); }
-      else { if (ext_cold == 0) CRT_EXTEND(false, 0, 0); else if (ext_cold == (int)kColdNormal) CRT_EXTEND(false, 0, kColdNormal); else CRT_EXTEND(false, 0, kColdAll); }
-#undef CRT_EXTEND
-#define CRT_SHADE(M, I, W, L) CRT_SHADE_D(M, I, W, L, false)
-#define CRT_SHADE0(I, W, L) do { if (drv) CRT_SHADE_D(0, I, W, L, true); else CRT_SHADE_D(0, I, W, L, false); } while (0)
-#define CRT_SHADE_D(M, I, W, L, D) \
-  timed(1, st, [&] { hipLaunchKernelGGL((k_shade<M, I, W, L, D>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (it == 0 ? 1 : 0) | ((int)it >= noclassify_from ? 2 : 0)); })
-      // the instance: material table (MATS), lights at infinity (INF), four waves (simple materials without lights at
-      // infinity, when the scene runs the wide kernels), and — as for k_path — whether the light list is empty
-#define CRT_SHADE_ENV(M, D) \
-  timed(1, st, [&] { hipLaunchKernelGGL((k_shade_env<M, D>), dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (it == 0 ? 1 : 0) | ((int)it >= noclassify_from ? 2 : 0)); })
-      if (P.envs) {  // the light list holds a mapped dome: the instances with the environment arm
-        if (mats_kind == 2) CRT_SHADE_ENV(2, false);
-        else if (mats_kind == 1) CRT_SHADE_ENV(1, false);
-        else if (drv) CRT_SHADE_ENV(0, true);
-        else CRT_SHADE_ENV(0, false);
-      }
-      else if (mats_kind == 2) { if (P.has_inf_lights) CRT_SHADE(2, true, false, true); else if (lit) CRT_SHADE(2, false, false, true); else CRT_SHADE(2, false, false, false); }
-      else if (mats_kind == 1) { if (P.has_inf_lights) CRT_SHADE(1, true, false, true); else if (lit) CRT_SHADE(1, false, false, true); else CRT_SHADE(1, false, false, false); }
-      else if (P.has_inf_lights) CRT_SHADE0(true, false, true);
-      else if (wide && !P.mat_index && shade_wide != 0) {
-        if (lit) CRT_SHADE0(false, true, true);
-        else if (shade_pipe_fits() && (int)it < noclassify_from) {  // the pipelined instance (shade_segment_pipe)
-          shade_piped = true;
-          timed(1, st, [&] {
-            if (drv) hipLaunchKernelGGL(k_shade_pipe<true>, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, it == 0 ? 1 : 0);
-            else hipLaunchKernelGGL(k_shade_pipe<false>, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, it == 0 ? 1 : 0);
-          });
-        }
-        else CRT_SHADE0(false, true, false);
-      }
-      else { if (lit) CRT_SHADE0(false, false, true); else CRT_SHADE0(false, false, false); }
-#undef CRT_SHADE_ENV
-#undef CRT_SHADE_D
-#undef CRT_SHADE0
-#undef CRT_SHADE
-      if (P.n_lights > 0 && P.strategy != CRT_STRATEGY_BSDF) {
-#define CRT_SHADOW(ST, W) \
-  timed(2, st, [&] { hipLaunchKernelGGL((k_shadow<ST, W>), dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats ? d_tstats + 1 : nullptr); })
-        if (cubic) timed(2, st, [&] {
-          if (d_tstats) hipLaunchKernelGGL(k_shadow_cubic<true>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats + 1);
-          else hipLaunchKernelGGL(k_shadow_cubic<false>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, (CrtTravStats *)nullptr);
-        });
-        else if (curve) timed(2, st, [&] {
-          if (d_tstats) hipLaunchKernelGGL(k_shadow_curve<true>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats + 1);
-          else hipLaunchKernelGGL(k_shadow_curve<false>, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, (CrtTravStats *)nullptr);
-        });
-        else if (d_tstats) { if (wide && !wdirect) CRT_SHADOW(true, 1); else CRT_SHADOW(true, 0); }
-#if CRT_WIDE_DIRECT_BUILD
-        else if (wdirect) CRT_SHADOW(false, 2);
-#endif
-        else { if (wide) CRT_SHADOW(false, 1); else CRT_SHADOW(false, 0); }
-#undef CRT_SHADOW
-      }
+      const int first = it == 0 ? 1 : 0;
+      timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
+      if (shade_pipe && (int)it < plan.noclassify_from)  // the pipelined instance (shade_segment_pipe)
+        timed(1, st, [&] { hipLaunchKernelGGL(shade_pipe, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, first); });
+      else
+        timed(1, st, [&] { hipLaunchKernelGGL(shade, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, first | ((int)it >= plan.noclassify_from ? 2 : 0)); });
+      if (shadow)
+        timed(2, st, [&] { hipLaunchKernelGGL(shadow, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats ? d_tstats + 1 : nullptr); });
       cur = 1 - cur;
     }
     return fold();
@@ -2290,9 +2161,9 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
     bool simple = true;
     for (size_t k = 0; k < n_materials; k++) simple = simple && material_class(materials[k]) <= 1;
     simple = simple && knobs.simple != 0;  // CRT_SIMPLE=0: the general instance (A/B, tests)
-    r.mats_kind = r.has_media ? 2 : (simple ? 0 : 1);
+    r.in.mats_kind = r.has_media ? 2 : (simple ? 0 : 1);
     // a curve image runs the general instances: no simple-material k_path is built with the rounded-cone arm
-    if ((P.scene.cold & kColdCurve) && r.mats_kind == 0) r.mats_kind = 1;
+    if ((P.scene.cold & kColdCurve) && r.in.mats_kind == 0) r.in.mats_kind = 1;
   }
   P.materials = r.d_materials; P.mat_derived = r.d_mat_derived; P.lights = r.d_lights; P.pixel_index = r.d_pixels;
   P.mat_class = r.d_mat_class;
@@ -2300,40 +2171,44 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   hipDeviceProp_t prop;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  // Pipeline by scene (see Renderer::fused; crt_internal.h, wide_split): small flat triangle scenes gain 4-9 % from
+  // Pipeline by scene (crt_internal.h: PlanInputs, wide_split): small flat triangle scenes gain 4-9 % from
   // the fourth wave per SIMD of the per-stage kernels; an instanced city loses 6 % to their four-entry LDS stack, and a
   // scene of analytic spheres only (openpbr_showcase: next to no traversal, all shading) 1 % to the hit records' round
   // trip (profiles/README.md).
   // select_engine decides, from the image, which engine instance runs it; CRT_WIDE=0/1 (A/B, tests) is a request it
   // honours only where the image can be decoded by what was asked for (never the four-wave kernels on direct words)
-  if (select_engine_env(P.scene, r.engine, true) != CRT_OK) {
+  if (select_engine_env(P.scene, r.in.engine, true) != CRT_OK) {
     set_error_text("crt_renderer_new: no traversal-engine instance of this build can decode the scene image");
     return nullptr;
   }
-  r.wide = r.engine.wide;
-  // ... and, once lanes overlap a batch's launches, every scene: the sphere-only showcase 12 176 -> 13 078 Mray/s (+7.4 %;
-  // round 2, one stream: -1 %). The fused kernel remains what small batches and the tails of large ones run.
-  r.prefer_stage = true;
-  if (knobs.prefer_stage >= 0) r.prefer_stage = knobs.prefer_stage != 0;  // the A/B knobs (crt_internal.h, Knobs): CRT_PREFER_STAGE ...
-  r.cam_compact_ok = knobs.cam_compact != 0;
-  r.root_cull_knob = knobs.root_cull;
+  // ... and, once lanes overlap a batch's launches, every scene prefers one launch per stage: the sphere-only showcase
+  // 12 176 -> 13 078 Mray/s (+7.4 %; round 2, one stream: -1 %). The fused kernel remains what small batches and the tails
+  // of large ones run.
+  PlanInputs &in = r.in;  // what P holds is copied per batch (plan_lane)
+  in.cam_compact_build = CRT_CAM_COMPACT_BUILD != 0; in.shade_pipe_build = kShadePipeBuild; in.root_cull_build = kRootCullBuild;
+  in.pipe_mat_max = kPipeMatMax;
+  // the A/B knobs (crt_internal.h, Knobs)
+  in.prefer_stage = knobs.prefer_stage != 0;  // CRT_PREFER_STAGE; unset: every scene does
+  in.cam_compact_ok = knobs.cam_compact != 0;
+  in.root_cull_knob = knobs.root_cull;
   r.estimate_root_miss_share();
-  r.noclassify_from = knobs.noclassify_from;
-  r.shade_pipe = knobs.shade_pipe;
-  r.mat_derived = knobs.mat_derived != 0;
-  r.tail_from = knobs.tail_from;
+  in.noclassify_from = knobs.noclassify_from;
+  in.shade_pipe = knobs.shade_pipe;
+  in.mat_derived = knobs.mat_derived != 0;
+  in.tail_from = knobs.tail_from;
+  in.shade_wide = knobs.shade_wide;
+  in.force_fused = knobs.fused;
+  in.stage_min_paths = knobs.stage_min_paths;
   r.max_batch_slots = knobs.max_batch_slots;
   r.n_lanes = knobs.lanes < 1 ? 1 : (knobs.lanes > Renderer::kMaxLanes ? Renderer::kMaxLanes : knobs.lanes);
   r.lane_min_paths = knobs.lane_min_paths;
-  r.shade_wide = knobs.shade_wide;
-  r.force_fused = knobs.fused;
-  r.stage_min_paths = knobs.stage_min_paths;
   // Workgroups per CU = queue segments per CU: Renderer::batch_grid.
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) r.cus = prop.multiProcessorCount;
-  r.stage_mult = r.wide ? 8 : 3;
+  r.stage_mult = in.engine.wide ? 8 : 3;
   if (knobs.grid_mult > 0) { r.fused_mult = r.stage_mult = knobs.grid_mult; r.mult_forced = 1; }  // CRT_GRID_MULT: tuning knob
-  r.fused = r.force_fused >= 0 ? r.force_fused != 0 : !r.prefer_stage;  // until the first batch: the scene's preference
-  r.grid = r.batch_grid(0, r.fused);
+  r.last_plan.fused = in.force_fused >= 0 ? in.force_fused != 0 : !in.prefer_stage;  // until the first batch: the scene's preference
+  r.last_plan.wide = !r.last_plan.fused && in.engine.wide;
+  r.grid = r.batch_grid(0, r.last_plan.fused);
   hold.p = nullptr;
   return R;
 }
@@ -2460,9 +2335,9 @@ int crt_renderer_set_lanes(CrtRenderer *r, int lanes) {
 }
 int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   if (!r || !out) return CRT_ERR_BAD_ARG;
-  out[0] = r->r.fused ? 1u : 0u;
-  out[1] = ((!r->r.fused && r->r.wide) ? 1u : 0u) | ((!r->r.fused && r->r.shade_piped) ? 2u : 0u) |
-           ((!r->r.fused && r->r.root_culled) ? 4u : 0u);
+  const LaunchPlan &plan = r->r.last_plan;  // every bit below is a per-stage one: plan_launches sets none of them on a fused plan
+  out[0] = plan.fused ? 1u : 0u;
+  out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

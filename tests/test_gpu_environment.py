@@ -209,7 +209,7 @@ def test_domelight_render_equals_the_hooked_reference_integrator(crt, oracle):
     assert np.isfinite(img).all() and img.max() > 0
 
 
-# Which shade instance a light list with a mapped dome runs follows from the material table (pathtrace.hip, CRT_SHADE_ENV):
+# Which shade instance a light list with a mapped dome runs follows from the material table (crt_internal.h, plan_launches: the k_shade_env rows):
 # simple materials k_shade_env<0, true> (derived records, the default) or <0, false> (CRT_MAT_DERIVED=0); any coat, fuzz or
 # thin-film material <1, false>; any material with an interior medium <2, false>. domelight itself is all simple, so each
 # of the other three is reached by changing one look of that scene.
