@@ -177,6 +177,8 @@ ABI_SYMBOLS = [
     "crt_shard_padded_count", "crt_gather_plan_new", "crt_gather_plan_free", "crt_gather_plan_padded_count",
     "crt_gather_plan_assemble", "crt_renderer_set_lanes",
     "crt_environment_new", "crt_environment_free", "crt_environment_tables", "crt_light_dome_mapped",
+    "crt_volumes_new", "crt_volumes_free", "crt_volumes_image", "crt_volumes_density_n", "crt_volumes_transmittance_n",
+    "crt_volumes_sample_n",
 ]
 
 _lib = None
@@ -298,6 +300,15 @@ def lib():
         L.crt_environment_free.argtypes = [vp]
         L.crt_environment_tables.argtypes = [vp, C.POINTER(CrtEnvironmentTables)]
         L.crt_light_dome_mapped.argtypes = [C.POINTER(CrtLight), fp, vp]
+    if hasattr(L, "crt_volumes_new"):  # volume regions (volumes.py)
+        L.crt_volumes_new.restype = vp
+        L.crt_volumes_new.argtypes = [vp, C.c_size_t, fp, C.c_size_t]
+        L.crt_volumes_free.restype = None
+        L.crt_volumes_free.argtypes = [vp]
+        L.crt_volumes_image.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.crt_volumes_density_n.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, vp]
+        L.crt_volumes_transmittance_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.crt_volumes_sample_n.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
     _lib = L
     return L
 
@@ -991,4 +1002,5 @@ from . import shard  # noqa: E402,F401  (pixel-tile sharding + the tile gather)
 from . import exr  # noqa: E402,F401  (EXR writer / reader + the reference's exr_diff metrics)
 from . import stats  # noqa: E402,F401  (RenderStats + the reference's report layout)
 from . import shading  # noqa: E402,F401  (Material / Light as batched device functions: the shading seam)
+from . import volumes  # noqa: E402,F401  (volume regions as batched device functions: fog and smoke behind the ABI)
 from . import synthetic  # noqa: E402,F401  (scenes built in code: the labelled stand-in for BASELINE config 5)

@@ -668,6 +668,14 @@ int device_ok();
 // environment with that id, or nothing when the id names none.
 int env_table_for_launch(const void **table);
 std::shared_ptr<void> env_retain(uint32_t id);
+// Volume regions (volumes.cpp). volumes_build_image: VolumeRegion::new for every record and the image the seam kernels
+// read, or CRT_ERR_BAD_ARG with the reason in crt_last_error. volumes_device: the device copy of a handle's image
+// (uploaded on first use) as the pointers the kernels take.
+namespace dev { struct VolRegionRec; }
+struct VolumesView { const dev::VolRegionRec *regions = nullptr; const float *grid = nullptr; uint32_t n_regions = 0; };
+int volumes_build_image(const CrtVolumeRegion *regions, size_t n, const float *grid, size_t grid_len, std::vector<unsigned char> &image);
+int volumes_device(CrtVolumes *v, VolumesView &out);
+uint32_t volumes_region_count(const CrtVolumes *v);
 // printf-style text for crt_last_error() on this thread (failures that are not HIP calls).
 void set_error_text(const char *fmt, ...);
 // Nothing may unwind through the C ABI — a host in C or Rust cannot catch it, and unwinding into its frames is undefined:

@@ -386,6 +386,7 @@ class SceneDesc:
         self.lights = []     # dicts: kind, geom_id, radiance, center/radius or origin/edge_u/edge_v/normal
         self.camera = None   # dict(lookfrom, lookat, vup, vfov_deg, aspect, aperture, focus_dist)
         self.settings = dict(DEFAULTS, strategy="power", filter="triangle", filter_radius=1.0)
+        self.volumes = []    # region dicts (volumes.region): only load(..., volumes=True) fills it; build_world ignores it
 
 
 def _triangulate(counts, indices, n_verts):  # usd_import.rs:1164-1214
@@ -530,13 +531,58 @@ def _dome_environment(prim, world, layer_dir):
                 light_to_world=np.stack(axes, axis=1).astype(np.float32))
 
 
-def load(path, width=None, height=None, cubic_curves=False, environment_maps=False):
+def _volume_region(prim, world):
+    """emit_volume (usd_import.rs:435-505): a prim carrying crust:volume:type as a region dict (volumes.region), or None
+    with a warning: unknown type, a grid without int[3] dims or without data, dims that do not match the data length. The
+    local box is [-size/2, size/2]^3 when the prim authors `size`, else the unit cube; the placement is the prim's
+    composed transform."""
+    import warnings
+    ty = prim.attr("crust:volume:type")
+    field = {}
+    if ty == "homogeneous":
+        field["field"] = "homogeneous"
+    elif ty == "smoke":
+        field = dict(field="noise", noise_scale=float(prim.attr("crust:volume:noiseScale", 4.0)),
+                     noise_octaves=max(int(prim.attr("crust:volume:noiseOctaves", 4)), 1),
+                     noise_gain=float(prim.attr("crust:volume:noiseGain", 0.5)),
+                     noise_lacunarity=float(prim.attr("crust:volume:noiseLacunarity", 2.0)),
+                     noise_threshold=float(prim.attr("crust:volume:noiseThreshold", 0.3)),
+                     noise_seed=int(prim.attr("crust:volume:noiseSeed", 0)) & 0xFFFFFFFF)
+    elif ty == "grid":
+        dims, data = prim.attr("crust:volume:gridDims"), prim.attr("crust:volume:gridData")
+        if dims is None or data is None or len(dims) != 3:
+            warnings.warn(f"Volume at {prim.path}: grid type needs int[3] crust:volume:gridDims and float[] crust:volume:gridData, skipped")
+            return None
+        nx, ny, nz = (max(int(d), 1) for d in dims)
+        data = np.asarray(data, dtype=np.float32).reshape(-1)
+        if nx * ny * nz != data.size:
+            warnings.warn(f"Volume at {prim.path}: gridDims {nx}x{ny}x{nz} does not match gridData length {data.size}, skipped")
+            return None
+        field = dict(field="grid", grid_dims=(nx, ny, nz), grid_data=data)
+    else:
+        warnings.warn(f"Volume at {prim.path}: unknown crust:volume:type \"{ty}\" (expected homogeneous | smoke | grid), skipped")
+        return None
+
+    def colour(name, default):
+        v = prim.attr(name)
+        return tuple(float(f32(c)) for c in v) if v is not None else (default,) * 3
+    size = prim.attr("size")
+    half = float(f32(f32(size) * f32(0.5))) if size is not None else 0.5
+    return dict(local_to_world=affine12(world), half_extent=(half, half, half), sigma_s=colour("crust:volume:sigmaS", 0.5),
+                sigma_a=colour("crust:volume:sigmaA", 0.0), emission=colour("crust:volume:emission", 0.0),
+                g=float(prim.attr("crust:volume:anisotropy", 0.0)), density_scale=float(prim.attr("crust:volume:densityScale", 1.0)),
+                name=prim.name, **field)
+
+
+def load(path, width=None, height=None, cubic_curves=False, environment_maps=False, volumes=False):
     """Reads a .usda file into a SceneDesc. width/height override the RenderSettings resolution BEFORE the
     camera is built (the aspect ratio feeds Camera::new; the reference can only do this by editing the USD).
     cubic_curves: decode cubic BasisCurves prims into cubic spans (Geometry::CubicCurves) as the reference's importer
     does; by default they are named in a warning and skipped, as before the backend could trace them.
     environment_maps: decode a DomeLight's inputs:texture:file (a lat-long EXR beside the layer) into an environment the
-    dome importance-samples (usd_import.rs:2389-2460); by default the dome keeps its uniform colour, with a warning."""
+    dome importance-samples (usd_import.rs:2389-2460); by default the dome keeps its uniform colour, with a warning.
+    volumes: a prim carrying crust:volume:type becomes a region of desc.volumes and never geometry (usd_import.rs:190-209,
+    :435-505); by default such a prim is read as before: by its schema, without a warning."""
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:6] == b"\xfd7zXZ\x00":  # an .xz-compressed stage (scenes/stress.usda.xz: 15 MB of generated text, 0.7 MB packed)
@@ -690,6 +736,9 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
             elif prim.type == "BasisCurves":  # usd_import.rs:1487-1500 makes a part of it; this reader does not yet
                 import warnings
                 warnings.warn(f"BasisCurves {prim.path}: curves inside a prototype are not decoded, skipped")
+            elif volumes and prim.attr("crust:volume:type") is not None:  # usd_import.rs:1505-1511
+                import warnings
+                warnings.warn(f"Volume at {prim.path} is inside a prototype: volumes cannot be instanced, skipped")
             for c in composed_children(prim):
                 stack.append((c, this_local))
         return parts
@@ -785,6 +834,11 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
         if t == "PointInstancer":
             emit_point_instancer(prim, world)
             return None  # prototypes are drawn through the instancer, never on their own (usd_import.rs:205-207)
+        if volumes and prim.attr("crust:volume:type") is not None:  # checked before every geometry schema (usd_import.rs:190-209)
+            reg = _volume_region(prim, world)
+            if reg is not None:
+                desc.volumes.append(reg)
+            return world
         if t == "Mesh":  # emit_mesh (usd_import.rs:912-1003)
             mat = _material_of(prim, by_path)
             motion = prim.attr("crust:motion:translate")
@@ -1063,6 +1117,15 @@ def fill_material(m, overrides):
         else:
             setattr(m, k, float(f32(v)))
     return m
+
+
+def build_volumes(desc, api):
+    """The aggregate of a description's volume regions (api.volumes.Volumes), or None when it holds none. build_world
+    never calls this: the wavefront renderer does not read volumes yet."""
+    if not desc.volumes:
+        return None
+    keys = set(api.volumes.region())
+    return api.volumes.Volumes([{k: v for k, v in r.items() if k in keys} for r in desc.volumes])
 
 
 def build_world(desc, api, new_material):

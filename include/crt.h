@@ -482,6 +482,89 @@ int crt_renderer_profile_read(CrtRenderer *r, double out_ms[4], uint64_t out_lau
 int crt_render_samples_stats(CrtRenderer *r, uint32_t sample_begin, uint32_t sample_count, void *stream,
                              CrtTravStats host_stats[2]);
 
+/* Volume regions (volume.rs): the `Volumes` aggregate as callable device functions, for a host integrator that keeps
+ * its own trace_path (tracer.rs:1167-1254) on crt_intersect_n / crt_occluded_n and the shading seam. A region is an
+ * oriented box (a 3x4 placement applied to [-half, half]^3) filled with a density field; the aggregate samples one
+ * interaction along a segment (weighted delta tracking, Volumes::sample_interaction, volume.rs:409-486) and estimates
+ * transmittance (analytic when every crossed region is homogeneous, ratio tracking otherwise, volume.rs:492-536).
+ * The wavefront renderer does not read volumes yet. Departures from the reference:
+ *  - a walk is bounded: after CRT_VOLUME_MAX_STEPS collision candidates it stops with status CRT_VOLUME_STEP_LIMIT and
+ *    an all-zero result (the reference loops for ever on a NaN distance or an infinite segment);
+ *  - at most CRT_VOLUME_MAX_REGIONS regions per aggregate (also the lobe capacity of a scatter record) and
+ *    CRT_VOLUME_MAX_OCTAVES noise octaves (the reference's octave loop has a 32-bit trip count);
+ *  - the placement is a 3x4 affine (crt_attach_instance's layout: three columns, then the translation), inverted by
+ *    the library's affine inverse; a placement without a finite inverse is refused.
+ * The free-path random numbers are the project's own stream: u = unit_f32(pcg_hash(s)), s = s * 747796405 + 2891336453,
+ * starting at the query's seed. */
+#define CRT_VOLUME_MAX_STEPS 65536u
+#define CRT_VOLUME_MAX_REGIONS 8u
+#define CRT_VOLUME_MAX_OCTAVES 32u
+enum { CRT_VOLUME_HOMOGENEOUS = 0, CRT_VOLUME_NOISE = 1, CRT_VOLUME_GRID = 2 }; /* DensityField, volume.rs:23-48 */
+enum { CRT_VOLUME_OK = 0, CRT_VOLUME_STEP_LIMIT = 1 };                          /* status of a walk */
+enum { CRT_VOLUME_PASSTHROUGH = 0, CRT_VOLUME_SCATTER = 1 };                    /* VolumeEvent, volume.rs:328-354 */
+
+/* The arguments of VolumeRegion::new (volume.rs:195-204). 152 bytes. */
+typedef struct CrtVolumeRegion {
+  float local_to_world[12];
+  float half_extent[3];
+  float sigma_s[3];
+  float sigma_a[3];
+  float g;
+  float emission[3];
+  float density_scale;
+  uint32_t field;            /* CRT_VOLUME_HOMOGENEOUS / _NOISE / _GRID */
+  float noise_scale;
+  uint32_t noise_octaves;
+  float noise_gain, noise_lacunarity, noise_threshold;
+  uint32_t noise_seed;
+  uint32_t grid_dims[3];     /* x fastest: index = x + nx * (y + ny * z) */
+  uint32_t grid_offset;      /* first float of this region's voxels in the grid array */
+  uint32_t grid_count;       /* how many floats it holds there: must equal nx * ny * nz */
+} CrtVolumeRegion;
+
+/* One segment: (t_eps, t_max) along origin + t * direction (the direction is not normalised). 48 bytes. */
+typedef struct CrtVolumeQuery {
+  float origin[3]; float t_eps;
+  float direction[3]; float t_max;
+  uint32_t seed; uint32_t _pad[3];
+} CrtVolumeQuery;
+
+/* 16 bytes. */
+typedef struct CrtVolumeTransmittance {
+  float transmittance[3];
+  uint32_t status;
+} CrtVolumeTransmittance;
+
+/* VolumeEvent (volume.rs:328-354). 144 bytes. A passthrough has t = 0, p = 0, n_lobes = 0 and its transmittance in
+ * `weight`; `emitted` is pre-weighted in both kinds. dir / pdf: PhaseMix::sample and max(PhaseMix::pdf, 1e-6)
+ * (tracer.rs:1193-1196) of a scatter when the call was given phase numbers, else zeros. */
+typedef struct CrtVolumeEvent {
+  float p[3]; float t;
+  float weight[3]; uint32_t kind;
+  float emitted[3]; uint32_t n_lobes;
+  float dir[3]; float pdf;
+  float lobes[CRT_VOLUME_MAX_REGIONS][2]; /* (weight, g); the weights sum to 1 */
+  uint32_t status; uint32_t _pad[3];
+} CrtVolumeEvent;
+
+typedef struct CrtVolumes CrtVolumes;
+/* Volumes::new over VolumeRegion::new: host only. `grid` holds every grid region's voxels (grid_len floats; NULL when
+ * no region is a grid). NULL with the reason in crt_last_error: more than CRT_VOLUME_MAX_REGIONS regions, a non-finite
+ * field of a record, an unknown field kind, more than CRT_VOLUME_MAX_OCTAVES octaves, grid dims whose product is 0 or
+ * is not grid_count, a grid range outside the array, a placement without a finite inverse. */
+CrtVolumes *crt_volumes_new(const CrtVolumeRegion *regions, size_t n, const float *grid, size_t grid_len);
+void crt_volumes_free(CrtVolumes *v);
+/* The image the kernels read (host memory, owned by the handle): a 256-byte header, the region records, the grid data. */
+int crt_volumes_image(const CrtVolumes *v, const void **image, size_t *bytes);
+/* VolumeRegion::density (volume.rs:234-242) of region `region` at n world points (3 floats each). */
+int crt_volumes_density_n(CrtVolumes *v, uint32_t region, const float *d_points, size_t n, float *d_density, void *stream);
+/* Volumes::transmittance (volume.rs:492-536). */
+int crt_volumes_transmittance_n(CrtVolumes *v, const CrtVolumeQuery *d_queries, size_t n, CrtVolumeTransmittance *d_out,
+                                void *stream);
+/* Volumes::sample_interaction (volume.rs:409-486); d_phase_u: NULL, or 3 floats per query (lobe_u, hg_u, hg_v). */
+int crt_volumes_sample_n(CrtVolumes *v, const CrtVolumeQuery *d_queries, const float *d_phase_u, size_t n,
+                         CrtVolumeEvent *d_events, void *stream);
+
 /* Library / device info. crt_last_error: text of the last failing HIP call on this thread ("" if none). */
 const char *crt_version(void);
 const char *crt_last_error(void);

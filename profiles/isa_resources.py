@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel resource usage and static instruction mix from the gfx950 ISA (no GPU needed: hipcc cross-compiles).
     python profiles/isa_resources.py > profiles/r02_isa_resources.txt
+    python profiles/isa_resources.py kernels/volume_seam.hip      (other device sources, relative to csrc/)
 Compiles kernels/pathtrace.hip and kernels/traverse.hip to assembly with the Makefile's flags and reads the
 `amdhsa.kernels` metadata (VGPRs, spilled VGPRs, SGPRs spilled to VGPR lanes, scratch and LDS bytes) and counts the
 instruction classes of each kernel's body; `div` and `sqrt` are the IEEE f32 divisions (one v_div_fixup_f32 each) and
@@ -11,7 +12,7 @@ CSRC = os.path.join(ROOT, "crust-render_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I../../include",
          "-fno-slp-vectorize", "-O2", "-mllvm", "-amdgpu-set-wave-priority", "--cuda-device-only", "-S"]
 print("%-64s %5s %6s %6s %7s %6s | %6s %6s %6s %7s %5s %5s %7s %5s %5s" % ("kernel", "vgpr", "vspill", "sspill", "scratch", "lds", "instr", "valu", "v_mov", "cndmask", "vmem", "lds", "lane_rw", "div", "sqrt"))
-for src in ("kernels/pathtrace.hip", "kernels/traverse.hip"):
+for src in (sys.argv[1:] or ("kernels/pathtrace.hip", "kernels/traverse.hip")):  # or the sources named on the command line
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + [src, "-o", tmp.name], cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
         s = open(tmp.name).read()
