@@ -882,13 +882,14 @@ class Renderer:
         return {n: (int(w[k]), (l[k] / (64.0 * w[k])) if w[k] else 0.0) for k, n in enumerate(self.SHADE_CLASSES)}
 
     def pipeline(self):
-        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'grid'}: the launch pipeline chosen for this scene (crt.h,
-        crt_renderer_pipeline); shade_pipe: the last batch's shade launches were the pipelined four-wave instance;
-        root_cull: its generate launches finished the camera rays that miss every child of the root."""
+        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'slim_state', 'grid'}: the launch pipeline chosen for this scene
+        (crt.h, crt_renderer_pipeline); shade_pipe: the last batch's shade launches were the pipelined four-wave instance;
+        root_cull: its generate launches finished the camera rays that miss every child of the root; slim_state: the
+        pipelined launches handed each other the slim path state (a material table in which nothing emits)."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
         return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
-                    grid=int(out[2]))
+                    slim_state=bool(out[1] & 8), grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""

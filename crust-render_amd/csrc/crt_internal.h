@@ -426,6 +426,10 @@ struct InstanceKey {  // a kernel template and its arguments, in the template's 
   X(SHADE_ENV, k_shade_env, 0, true) X(SHADE_ENV, k_shade_env, 0, false) X(SHADE_ENV, k_shade_env, 1, false) X(SHADE_ENV, k_shade_env, 2, false)
 #define CRT_INSTANCES_SHADE_PIPE(X) /* k_shade_pipe<DRV> */ \
   X(SHADE_PIPE, k_shade_pipe, true) X(SHADE_PIPE, k_shade_pipe, false)
+// k_shade_pipe<DRV, true>: the instances that carry the slim path state between two of their launches (LaunchPlan::
+// slim_state). A list of their own: a plan names them through shade_slim_key(), never in shade_early.
+#define CRT_INSTANCES_SHADE_PIPE_SLIM(X) /* k_shade_pipe<DRV, SLIM> */ \
+  X(SHADE_PIPE, k_shade_pipe, true, true) X(SHADE_PIPE, k_shade_pipe, false, true)
 #define CRT_INSTANCES_SHADOW(X) /* k_shadow<STATS, WIDE>, k_shadow_curve<STATS>, k_shadow_cubic<STATS> */ \
   X(SHADOW, k_shadow, false, 0) X(SHADOW, k_shadow, false, 1) CRT_WIDE_DIRECT_INSTANCES_SHADOW(X) X(SHADOW, k_shadow, true, 0) X(SHADOW, k_shadow, true, 1) \
   X(SHADOW_CURVE, k_shadow_curve, false) X(SHADOW_CURVE, k_shadow_curve, true) X(SHADOW_CUBIC, k_shadow_cubic, false) X(SHADOW_CUBIC, k_shadow_cubic, true)
@@ -455,6 +459,8 @@ struct PlanInputs {
   int noclassify_from = 1 << 30;  // CRT_NOCLASSIFY_FROM: per-stage shade without its CLASSIFY pass from this bounce on
   int shade_wide = -1;            // CRT_SHADE_WIDE: 0 = the three-wave shade kernels even beside four-wave traversal kernels (A/B)
   int shade_pipe = 1;             // CRT_SHADE_PIPE: 0 = never the pipelined four-wave shade kernel (A/B, tests)
+  int slim_state = 1;             // CRT_SLIM_STATE: 0 = the pipelined kernel carries the full path state between its launches (A/B, tests)
+  bool no_emitter = false;        // no record of the material table can emit (table_has_no_emitter, at creation)
   bool cam_compact_ok = true;     // CRT_CAM_COMPACT
   int root_cull_knob = -1;        // CRT_ROOT_CULL: 0 = generate never finishes a camera ray, 1 = wherever the rule allows (A/B, tests)
   float root_miss_share = 0.0f;   // share of a coarse grid of camera rays that misses every child of the root (pathtrace.hip)
@@ -476,6 +482,22 @@ inline bool shade_pipe_fits(const PlanInputs &q) {
   return q.shade_pipe_build && q.shade_pipe != 0 && q.mats_kind == 0 && q.n_lights == 0 && !q.has_motion && !q.mat_index &&
          q.partition == 0 && !q.class_stats && q.n_materials <= (uint32_t)q.pipe_mat_max;
 }
+// True where NO record of a material table can emit: radiance gathered along a path is then +0 at every vertex, and the
+// pipelined shade kernel need not carry it. A sufficient condition without arithmetic — a record's emission is
+// emission_color for an Emissive and emission_color * emission_luminance for every other kind (shade.hip.h, emission()):
+// either all three colour components compare equal to 0 (and the luminance they are multiplied by is finite), or a
+// non-Emissive record has luminance 0 and a finite colour. A NaN anywhere fails both, so it counts as an emitter.
+inline bool table_has_no_emitter(const CrtMaterial *m, size_t n) {
+  auto finite = [](float x) { return x - x == 0.0f; };  // false for NaN and the infinities
+  for (size_t k = 0; k < n; k++) {
+    const float *c = m[k].emission_color, lum = m[k].emission_luminance;
+    const bool emissive = m[k].kind == CRT_MAT_EMISSIVE;
+    const bool black = c[0] == 0.0f && c[1] == 0.0f && c[2] == 0.0f && (emissive ? lum == lum : finite(lum));
+    const bool dark = !emissive && lum == 0.0f && finite(c[0]) && finite(c[1]) && finite(c[2]);
+    if (!black && !dark) return false;
+  }
+  return true;
+}
 struct LaunchPlan {
   bool fused = true;              // one k_path launch for the whole path loop; otherwise one launch per stage and bounce
   bool wide = false;              // per-stage: the four-wave traversal kernels
@@ -488,6 +510,15 @@ struct LaunchPlan {
   InstanceKey path, extend, shade, shade_early, shadow_key;  // path: the fused launch or the tail; shade_early: the
                                   // pipelined instance, which runs the bounces before noclassify_from; none = not launched
   bool shade_piped() const { return !shade_early.none(); }
+  // The pipelined kernel's launches hand each other the SLIM path state (kernels/pathtrace.hip, PathSoA): three planes,
+  // without the words every live path of a launch shares and without the radiance, which is +0 where nothing emits. A
+  // field of its own — shade_early names the same instance whatever this says; render_lane launches shade_slim_key().
+  bool slim_state = false;
+  InstanceKey shade_slim_key() const {
+    InstanceKey k = slim_state ? shade_early : InstanceKey{};
+    if (slim_state) k.arg[1] = 1;
+    return k;
+  }
 };
 // The EngineSelect a traversal instance of width w amounts to on this image (0 = three waves, 1 = four, the flat engine
 // copy only, 2 = four, the direct copy only) — run_traversal picks the three-wave kernels' copy from the image.
@@ -558,6 +589,7 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
     const bool shade_wide = simple && !q.has_inf_lights && pl.wide && !q.mat_index && q.shade_wide != 0;
     pl.shade = q.has_env ? key(KF_SHADE_ENV, q.mats_kind, drv) : key(KF_SHADE, q.mats_kind, q.has_inf_lights, shade_wide, lit, drv);
     if (shade_wide && shade_pipe_fits(q) && q.noclassify_from > 0) pl.shade_early = key(KF_SHADE_PIPE, drv);
+    pl.slim_state = pl.shade_piped() && q.no_emitter && q.slim_state != 0;
     if (pl.shadow) {
       if (e.curve) { pl.shadow_key = key(e.cubic ? KF_SHADOW_CUBIC : KF_SHADOW_CURVE, q.stats); shadow_cold = curve_cold; }
       else pl.shadow_key = key(KF_SHADOW, q.stats, width);
@@ -566,7 +598,7 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
   const bool ok = (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
                   (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = InstanceKey{};
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = InstanceKey{}; pl.slim_state = false; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }
@@ -593,6 +625,7 @@ struct Knobs {
   // renderer
   int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, root_cull = -1, shade_wide = -1, shade_pipe = 1, fused = -1;
   int mat_derived = 1;        // CRT_MAT_DERIVED: 0 = the shade kernels compute the per-material constants at every vertex again
+  int slim_state = 1;         // CRT_SLIM_STATE: 0 = the pipelined shade kernel hands itself the full path state
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
 };

@@ -109,6 +109,14 @@ struct PathSoA {
                 // + carried-medium id (high 14)
   float4 *e;    // previous vertex position + previous bounce pdf (PrevBounce, tracer.rs:899-906); lit scenes only
   float *time;  // shutter time; scenes with motion only
+  // The SLIM form, between two launches of k_shade_pipe<DRV, true> only (LaunchPlan::slim_state: no record of the
+  // material table emits, so L is +0 at every vertex; no media, so no carried medium):
+  //   a, b  as above
+  //   c     beta.z | sampler pattern (bits) | owned-pixel index + kPrevDelta-bit << 31 (bits) | sample-in-batch (bits)
+  //   d     neither written nor read: n_rec and the remaining depth follow from the bounce number, which the launch
+  //         is told, kPrevValid is "not the first bounce"
+  // 48 bytes per path instead of 64. Every other consumer (k_extend reads a and b in either form; k_shade, k_path) sees
+  // the full form: the launch before it is told to write that (out_full).
 };
 struct HitSoA { float4 *h; uint32_t *geom; };  // t, ray-facing normal; geom id | front_face << 31, ~0 = miss
 struct ShadowSoA { float4 *a, *b, *c; };       // origin + tmax; dir + time; contribution + target (bits)
@@ -1154,6 +1162,17 @@ constexpr int kPipeMatMax = (kArenaWide - kSobolLdsWords - kPipeRingDwords - kPi
 static_assert(kPipeMatMax >= 6 && kSobolLdsWords + kPipeMatMax * kMatDwords + kPipeRingDwords + kPipeStageDwords <= kArenaWide,
               "Sobol tables + material table + rings + staging blocks fit the four-wave arena");
 static_assert((kArenaWide - kPipeStageDwords) % 4 == 0 && kPipeWaveDwords % 4 == 0, "staging planes are 16-byte aligned");
+// The SLIM instances (k_shade_pipe<DRV, true>): a hit-ring entry is the slot number AND the hit word CLASSIFY already
+// holds (a vertex step takes it from there: no 4-byte fetch of it again, no staging row for it), and a wave's block is
+// four planes — a, b, c or d, h: the first bounce reads plane d and no plane c, every later one the slim plane c and no
+// plane d, so the two share a place. The wider ring is paid for by that plane.
+constexpr int kSlimWaveDwords = 4 * 256;
+constexpr int kSlimStageDwords = (kBlock / 64) * kSlimWaveDwords;
+constexpr int kSlimRingDwords = 3 * (int)kPipeRing;  // hits: two dwords per entry; misses: one
+static_assert(kSobolLdsWords + kPipeMatMax * kMatDwords + kSlimRingDwords + kSlimStageDwords <= kArenaWide,
+              "the slim layout holds the same material table (kPipeMatMax is the host's one rule for both)");
+static_assert((kArenaWide - kSlimStageDwords) % 4 == 0 && (kArenaWide - kSlimStageDwords - kSlimRingDwords) % 2 == 0,
+              "slim staging planes are 16-byte aligned, hit-ring entries 8-byte aligned");
 constexpr bool kShadePipeBuild = kBins == 1 && !kRegenFirst && CRT_SHADE_WIDE_WAVES == 4;
 #ifndef CRT_SHADE_PIPE_HIT_REGS
 #define CRT_SHADE_PIPE_HIT_REGS 0  // 1: the hit record of a vertex step by register loads at the top of the step, not staged (A/B)
@@ -1176,10 +1195,12 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 
 // Stamps (CRT_SHADE_STAMPS): [0] waiting for the staged state, [1] classify rounds with their barriers, [2] picking and
 // requesting the next step, [3] vertex steps, [4] miss steps, [5] iterations, [6] rounds.
-template <bool DRV>
+// SLIM: the instance that reads the slim path state (PathSoA) at every bounce but the first — `it` is the bounce number
+// — and writes it unless out_full (the next consumer of N is not this kernel: k_path's tail, k_shade, nothing).
+template <bool DRV, bool SLIM>
 __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                                    Counters *C, int cur, float4 *staging, uint32_t *arena /* kArenaWide */,
-                                                   bool first) {
+                                                   bool first, uint32_t it, bool out_full) {
   constexpr bool STAMPS = CRT_SHADE_STAMPS != 0;
   __shared__ uint32_t lds_ctr[10];   // [2..8] statistics
   __shared__ uint32_t out_n;         // survivors
@@ -1201,8 +1222,10 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
     for (uint32_t w = threadIdx.x; w < words; w += kBlock) mat_lds[w] = src[w];
   }
   const typename MatTable<DRV>::Rec *mats = reinterpret_cast<const typename MatTable<DRV>::Rec *>(mat_lds);
-  uint32_t *ring_h = arena + kArenaWide - kPipeStageDwords - kPipeRingDwords, *ring_m = ring_h + kPipeRing;
-  uint32_t *stg = arena + kArenaWide - kPipeStageDwords + (threadIdx.x >> 6) * kPipeWaveDwords;  // this wave's block
+  constexpr int STAGE = SLIM ? kSlimStageDwords : kPipeStageDwords, WAVE = SLIM ? kSlimWaveDwords : kPipeWaveDwords;
+  constexpr int RINGS = SLIM ? kSlimRingDwords : kPipeRingDwords;
+  uint32_t *ring_h = arena + kArenaWide - STAGE - RINGS, *ring_m = ring_h + (SLIM ? 2 : 1) * kPipeRing;
+  uint32_t *stg = arena + kArenaWide - STAGE + (threadIdx.x >> 6) * WAVE;  // this wave's block
   const uint32_t lane = threadIdx.x & 63;
   __syncthreads();
   const uint32_t seg0 = blockIdx.x * P.seg_cap;  // kBins == 1: slot of the k-th live path = seg0 + k
@@ -1216,6 +1239,7 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
   uint32_t next_in = 0, head_h = 0, head_m = 0, tail_h = 0, tail_m = 0;  // uniform
   uint32_t hg_next = threadIdx.x < n ? H.geom[seg0 + threadIdx.x] : kInvalid;  // the hit words of the next classify round
   uint32_t kind = 0, take = 0, k_in = 0;  // the current step: 0 none yet, 1 vertex, 2 miss; its entries' states are on their way
+  uint32_t head_in = 0;                   // SLIM: where the current vertex step's entries sit in the hit ring (uniform)
   if (STAMPS) t0 = __builtin_readcyclecounter();
   for (;;) {
     // ---- the current step's state: out of this wave's staging block, into registers ----
@@ -1223,7 +1247,30 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
     float4 hh = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     uint4 D = make_uint4(0u, 0u, 0u, 0u);
     uint32_t hg = kInvalid;
-    if (kind) {
+    if (SLIM && kind) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's loads into its own block have landed
+      A = reinterpret_cast<const float4 *>(stg)[lane];
+      if (!first) {  // the slim form: L is +0, the depth words follow from the bounce number
+        B = reinterpret_cast<const float4 *>(stg + 256)[lane];
+        const float4 X = reinterpret_cast<const float4 *>(stg + 512)[lane];
+        const uint32_t px = __float_as_uint(X.z);
+        Cc = make_float4(X.x, 0.0f, 0.0f, 0.0f);
+        D = make_uint4(__float_as_uint(X.y), px & 0x7fffffffu, (it & 0xffffu) | (((P.max_depth - it) & 0xffffu) << 16),
+                       __float_as_uint(X.w) | kPrevValid | ((px >> 31) ? kPrevDelta : 0u));
+      } else if (!compact) {
+        B = reinterpret_cast<const float4 *>(stg + 256)[lane];
+        D = reinterpret_cast<const uint4 *>(stg + 512)[lane];
+      } else if (compact_d) {
+        D = reinterpret_cast<const uint4 *>(stg + 512)[lane];
+      }
+      if (kind == 1) {
+        // the hit word from the ring entry: nothing appends between a step's pick and this read (the next CLASSIFY
+        // round starts behind a barrier every wave reaches after it)
+        hh = CRT_SHADE_PIPE_HIT_REGS ? H.h[seg0 + k_in] : reinterpret_cast<const float4 *>(stg + 768)[lane];
+        hg = ring_h[2 * ((head_in + threadIdx.x) % kPipeRing) + 1];
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ... and are in registers: the block may be overwritten
+    } else if (kind) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's loads into its own block have landed
       A = reinterpret_cast<const float4 *>(stg)[lane];
       if (!compact) {
@@ -1253,7 +1300,8 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
       if (next_in + threadIdx.x < n) hg_next = H.geom[seg0 + next_in + threadIdx.x];
       const bool hit = k_c < n && hg_c != kInvalid, miss = k_c < n && hg_c == kInvalid;
       const uint32_t at_h = seg_append(hit, &ring_tail[0]);
-      if (hit) ring_h[at_h % kPipeRing] = k_c;
+      if (SLIM) { if (hit) reinterpret_cast<uint2 *>(ring_h)[at_h % kPipeRing] = make_uint2(k_c, hg_c); }
+      else if (hit) ring_h[at_h % kPipeRing] = k_c;
       const uint32_t at_m = seg_append(miss, &ring_tail[1]);
       if (miss) ring_m[at_m % kPipeRing] = k_c;
       lds_barrier();
@@ -1267,7 +1315,22 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
     uint32_t kind_n = 0, take_n = 0, k_n = 0;
     if (pend_h >= (uint32_t)kBlock || (pend_h && pend_m < (uint32_t)kBlock)) { kind_n = 1; take_n = pend_h < (uint32_t)kBlock ? pend_h : (uint32_t)kBlock; }
     else if (pend_m) { kind_n = 2; take_n = pend_m < (uint32_t)kBlock ? pend_m : (uint32_t)kBlock; }
-    if (kind_n && threadIdx.x < take_n) {
+    const uint32_t head_n = head_h;
+    if (SLIM && kind_n && threadIdx.x < take_n) {
+      k_n = kind_n == 1 ? ring_h[2 * ((head_h + threadIdx.x) % kPipeRing)] : ring_m[(head_m + threadIdx.x) % kPipeRing];
+      const uint32_t i_n = seg0 + k_n;
+      lds_dma16(&S.a[i_n], stg);
+      if (!first) {
+        lds_dma16(&S.b[i_n], stg + 256);
+        lds_dma16(&S.c[i_n], stg + 512);
+      } else if (!compact) {
+        lds_dma16(&S.b[i_n], stg + 256);
+        lds_dma16(&S.d[i_n], stg + 512);
+      } else if (compact_d) {
+        lds_dma16(&S.d[i_n], stg + 512);
+      }
+      if (kind_n == 1 && !CRT_SHADE_PIPE_HIT_REGS) lds_dma16(&H.h[i_n], stg + 768);
+    } else if (kind_n && threadIdx.x < take_n) {
       k_n = kind_n == 1 ? ring_h[(head_h + threadIdx.x) % kPipeRing] : ring_m[(head_m + threadIdx.x) % kPipeRing];
       const uint32_t i_n = seg0 + k_n;
       lds_dma16(&S.a[i_n], stg);
@@ -1384,9 +1447,13 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
       if (alive) {
         st_nt(&N.a[j], make_float4(n_o.x, n_o.y, n_o.z, n_d.x));
         st_nt(&N.b[j], make_float4(n_d.y, n_d.z, beta.x, beta.y));
-        st_nt(&N.c[j], make_float4(beta.z, L.x, L.y, L.z));
-        st_nt(&N.d[j], make_uint4(pattern, pix, ((meta & 0xffffu) + 1u) | (((meta >> 16) - 1u) << 16),
-                                  sl | kPrevValid | (n_delta ? kPrevDelta : 0u)));
+        if (SLIM && !out_full) {  // uniform: the next launch on this buffer is this kernel again
+          st_nt(&N.c[j], make_float4(beta.z, __uint_as_float(pattern), __uint_as_float(pix | (n_delta ? 0x80000000u : 0u)), __uint_as_float(sl)));
+        } else {
+          st_nt(&N.c[j], make_float4(beta.z, L.x, L.y, L.z));
+          st_nt(&N.d[j], make_uint4(pattern, pix, ((meta & 0xffffu) + 1u) | (((meta >> 16) - 1u) << 16),
+                                    sl | kPrevValid | (n_delta ? kPrevDelta : 0u)));
+        }
       } else if (active) {
         st_nt(&staging[sl * P.n_act + pix], make_float4(L.x, L.y, L.z, 0.0f));
       }
@@ -1394,7 +1461,7 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
     }
     if (STAMPS) t_acc[5]++;
     if (!kind_n) break;  // uniform: input exhausted and nothing pending
-    kind = kind_n; take = take_n; k_in = k_n;
+    kind = kind_n; take = take_n; k_in = k_n; head_in = head_n;
   }
   add_stat(&lds_ctr[2], s_closest); add_stat(&lds_ctr[4], s_vertices);
   add_stat(&lds_ctr[5], s_rr_t); add_stat(&lds_ctr[6], s_rr_k); add_stat(&lds_ctr[7], s_esc);
@@ -1410,11 +1477,13 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
   if (STAMPS && lane == 0)
     for (int s = 0; s < 7; s++) atomicAdd(s < 4 ? &C->cls_waves[s] : &C->cls_lanes[s - 4], t_acc[s]);
 }
-template <bool DRV>
+// it, out_full: read by the SLIM instances only.
+template <bool DRV, bool SLIM = false>
 __global__ __launch_bounds__(kBlock, CRT_SHADE_WIDE_WAVES) void k_shade_pipe(Params P, PathSoA S, PathSoA N, HitSoA H, Counters *C,
-                                                                              int cur, float4 *staging, int first) {
+                                                                              int cur, float4 *staging, int first, uint32_t it,
+                                                                              int out_full) {
   __shared__ __attribute__((aligned(16))) uint32_t arena[kArenaWide];
-  shade_segment_pipe<DRV>(P, S, N, H, C, cur, staging, arena, first != 0);
+  shade_segment_pipe<DRV, SLIM>(P, S, N, H, C, cur, staging, arena, first != 0, it, out_full != 0);
 }
 
 // ---- shadow: World::occluded (rt_world.rs:235-237) for the queue; unoccluded requests pay out ----
@@ -1611,7 +1680,7 @@ __global__ __launch_bounds__(kBlock) void k_film_out(const float4 *film, uint32_
 using ExtendFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, CrtTravStats *);
 using PathFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, float4 *, uint32_t, uint32_t, uint32_t, int);
 using ShadeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int);
-using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int);
+using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int, uint32_t, int);
 using ShadowFn = void (*)(Params, PathSoA, ShadowSoA, Counters *, float4 *, CrtTravStats *);
 template <class Fn>
 struct InstanceRow { InstanceKey key; Fn fn; };
@@ -1619,7 +1688,7 @@ struct InstanceRow { InstanceKey key; Fn fn; };
 static const InstanceRow<ExtendFn> kExtendRows[] = {CRT_INSTANCES_EXTEND(CRT_ROW)};
 static const InstanceRow<PathFn> kPathRows[] = {CRT_INSTANCES_PATH(CRT_ROW)};
 static const InstanceRow<ShadeFn> kShadeRows[] = {CRT_INSTANCES_SHADE(CRT_ROW)};
-static const InstanceRow<ShadePipeFn> kShadePipeRows[] = {CRT_INSTANCES_SHADE_PIPE(CRT_ROW)};
+static const InstanceRow<ShadePipeFn> kShadePipeRows[] = {CRT_INSTANCES_SHADE_PIPE(CRT_ROW) CRT_INSTANCES_SHADE_PIPE_SLIM(CRT_ROW)};
 static const InstanceRow<ShadowFn> kShadowRows[] = {CRT_INSTANCES_SHADOW(CRT_ROW)};
 #undef CRT_ROW
 // The kernel a key names (nullptr for the empty key: nothing to launch); false when the build holds no such instance.
@@ -1914,7 +1983,13 @@ struct Renderer {
     p.seg_cap = (uint32_t)(((total + (size_t)grid * kBlock - 1) / ((size_t)grid * kBlock)) * kBlock);
     p.cam_compact = last_plan.cam_compact;
     p.root_cull = last_plan.root_cull ? 1u : 0u;
-    return ensure_buffers(B, (size_t)p.seg_cap * grid);  // >= total: the staging film's (sample, active pixel) slots too
+    if (const int rc = ensure_buffers(B, (size_t)p.seg_cap * grid)) return rc;  // >= total: the staging film's (sample, active pixel) slots too
+    // the slim path state keeps a flag in bit 31 of the pixel word: pixel < n_act <= slots < 2^31 (ensure_buffers)
+    if (last_plan.slim_state && p.n_act > 0x7fffffffu) {
+      set_error_text("render refused: %u active pixels do not fit the slim path state's 31 bits", p.n_act);
+      return CRT_ERR_BAD_ARG;
+    }
+    return CRT_OK;
   }
 
   int render_lane(Lane &B, uint32_t sample_begin, uint32_t n_samples, hipStream_t st, CrtTravStats *d_tstats, bool fold_here) {
@@ -1933,10 +2008,11 @@ struct Renderer {
     PathFn path;
     ExtendFn extend;
     ShadeFn shade;
-    ShadePipeFn shade_pipe;
+    ShadePipeFn shade_pipe, shade_slim;
     ShadowFn shadow;
     if (!find_instance(kPathRows, plan.path, path) || !find_instance(kExtendRows, plan.extend, extend) ||
         !find_instance(kShadeRows, plan.shade, shade) || !find_instance(kShadePipeRows, plan.shade_early, shade_pipe) ||
+        !find_instance(kShadePipeRows, plan.shade_slim_key(), shade_slim) ||
         !find_instance(kShadowRows, plan.shadow_key, shadow))
       return CRT_ERR_UNSUPPORTED;
     float4 *staging = B.staging;
@@ -1972,9 +2048,14 @@ struct Renderer {
       }
       const int first = it == 0 ? 1 : 0;
       timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
-      if (shade_pipe && (int)it < plan.noclassify_from)  // the pipelined instance (shade_segment_pipe)
-        timed(1, st, [&] { hipLaunchKernelGGL(shade_pipe, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, first); });
-      else
+      if (shade_pipe && (int)it < plan.noclassify_from) {  // the pipelined instance (shade_segment_pipe)
+        // Slim state (plan.slim_state): the launch writes the full form where the next consumer of its output is not
+        // this kernel again — the tail, the plain k_shade from noclassify_from, or nothing past the depth limit.
+        const uint32_t nx = it + 1;
+        const int out_full = (nx <= P.max_depth && nx < plan.tail_at && (int)nx < plan.noclassify_from) ? 0 : 1;
+        const ShadePipeFn fn = shade_slim ? shade_slim : shade_pipe;
+        timed(1, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, first, it, out_full); });
+      } else
         timed(1, st, [&] { hipLaunchKernelGGL(shade, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, first | ((int)it >= plan.noclassify_from ? 2 : 0)); });
       if (shadow)
         timed(2, st, [&] { hipLaunchKernelGGL(shadow, dim3(grid), dim3(kBlock), 0, st, p, S[1 - cur], Q, C, staging, d_tstats ? d_tstats + 1 : nullptr); });
@@ -2194,6 +2275,8 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   r.estimate_root_miss_share();
   in.noclassify_from = knobs.noclassify_from;
   in.shade_pipe = knobs.shade_pipe;
+  in.slim_state = knobs.slim_state;
+  in.no_emitter = table_has_no_emitter(materials, n_materials);  // of the table the kernels read (deduplicated or not)
   in.mat_derived = knobs.mat_derived != 0;
   in.tail_from = knobs.tail_from;
   in.shade_wide = knobs.shade_wide;
@@ -2337,7 +2420,7 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   if (!r || !out) return CRT_ERR_BAD_ARG;
   const LaunchPlan &plan = r->r.last_plan;  // every bit below is a per-stage one: plan_launches sets none of them on a fused plan
   out[0] = plan.fused ? 1u : 0u;
-  out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u);
+  out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

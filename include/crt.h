@@ -456,7 +456,8 @@ int crt_renderer_shade_class_stats(CrtRenderer *r, int enable, uint64_t out_wave
  * bounce; out[1] = 1 when the traversal kernels are the four-workgroups-per-CU instances (flat triangle scenes: small
  * trees and, in the renderer, large ones; crt_scene_engine_select), | 2 when the shade launches were the pipelined
  * four-wave instance (unlit simple-material scenes of one material class whose material table fits its LDS arena beside
- * the staging blocks; CRT_SHADE_PIPE=0: never); out[2] = workgroups (= queue segments) per launch.
+ * the staging blocks; CRT_SHADE_PIPE=0: never), | 8 when those launches handed each other the slim 48-byte path state
+ * (a material table in which nothing emits; CRT_SLIM_STATE=0: never); out[2] = workgroups (= queue segments) per launch.
  * The renderer takes the per-stage form for batches of >= 96 Mi paths and the fused kernel for smaller ones and for the
  * tail of a large one. Environment CRT_FUSED / CRT_WIDE / CRT_STAGE_MIN_PATHS / CRT_GRID_MULT override. */
 int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]);
