@@ -180,6 +180,9 @@ ABI_SYMBOLS = [
     "crt_volumes_new", "crt_volumes_free", "crt_volumes_image", "crt_volumes_density_n", "crt_volumes_transmittance_n",
     "crt_volumes_sample_n",
 ]
+# include/crt_render_volumes.h: the entry point of volume renders, declared beside crt.h (whose 84 declarations the list
+# above mirrors) and exported by the same library.
+ABI_SYMBOLS_RENDER_VOLUMES = ["crt_renderer_set_volumes"]
 
 _lib = None
 
@@ -309,6 +312,8 @@ def lib():
         L.crt_volumes_density_n.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, vp]
         L.crt_volumes_transmittance_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.crt_volumes_sample_n.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "crt_renderer_set_volumes"):  # volume renders (absent from older A/B variant libraries)
+        L.crt_renderer_set_volumes.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -803,6 +808,7 @@ class Renderer:
         if not self.h:
             raise CrtError(-1, "crt_renderer_new")
         self.n_pix = lib().crt_renderer_pixel_count(self.h)
+        self.volumes = None  # the bound aggregate (set_volumes)
 
     def __del__(self):
         try:
@@ -818,6 +824,13 @@ class Renderer:
 
     def render_samples(self, sample_begin, sample_count, stream=None):
         _check(lib().crt_render_samples(self.h, sample_begin, sample_count, _stream_ptr(stream)), "crt_render_samples")
+
+    def set_volumes(self, vol):
+        """Binds a volume aggregate (volumes.Volumes) for the batches that follow, or detaches it (None): fog and smoke in
+        the wavefront renderer (crt_render_volumes.h, crt_renderer_set_volumes). The renderer keeps the aggregate alive; the image is
+        uploaded inside the call. Where no region is crossed the image equals the unbound renderer's bit for bit."""
+        _check(lib().crt_renderer_set_volumes(self.h, vol.h if vol is not None else None), "crt_renderer_set_volumes")
+        self.volumes = vol
 
     def render_samples_stats(self, sample_begin, sample_count, stream=None):
         st = (CrtTravStats * 2)()
@@ -882,14 +895,15 @@ class Renderer:
         return {n: (int(w[k]), (l[k] / (64.0 * w[k])) if w[k] else 0.0) for k, n in enumerate(self.SHADE_CLASSES)}
 
     def pipeline(self):
-        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'slim_state', 'grid'}: the launch pipeline chosen for this scene
+        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'slim_state', 'volumes', 'grid'}: the launch pipeline chosen for this scene
         (crt.h, crt_renderer_pipeline); shade_pipe: the last batch's shade launches were the pipelined four-wave instance;
         root_cull: its generate launches finished the camera rays that miss every child of the root; slim_state: the
-        pipelined launches handed each other the slim path state (a material table in which nothing emits)."""
+        pipelined launches handed each other the slim path state (a material table in which nothing emits); volumes: the
+        batch was a volume render (set_volumes: the volume stage ran between extend and shade)."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
         return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
-                    slim_state=bool(out[1] & 8), grid=int(out[2]))
+                    slim_state=bool(out[1] & 8), volumes=bool(out[1] & 16), grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""
@@ -960,17 +974,19 @@ def load_usda(path, width=None, height=None, max_depth=None, rank=0, world=1, va
     return r, desc
 
 def render_with_report(path, spp=None, out_exr=None, width=None, height=None, max_depth=None, variance=None,
-                       batch=16):
+                       batch=16, volumes=False):
     """The reference binary's run in one call (main.rs:491-648): load, commit, render, optionally write the EXR, and
     return (image, RenderStats) — the report carries the phases the reference prints ("Parse USD stage",
     "Commit acceleration structure", "Render", "Write image") and its scene / ray statistics blocks.
-    spp / variance default to the scene's own RenderSettings (adaptive stopping on, as the binary renders)."""
+    spp / variance default to the scene's own RenderSettings (adaptive stopping on, as the binary renders).
+    volumes: prims carrying crust:volume:type become the regions of an aggregate bound to the renderer (fog.usda,
+    smoke.usda); the report's "volume regions" row counts them."""
     import sys
     from . import stats as _stats
     st = _stats.RenderStats()
     me = sys.modules[__name__]
     with st.phase("Parse USD stage"):
-        desc = usda.load(path, width, height)
+        desc = usda.load(path, width, height, volumes=bool(volumes))
     s = desc.settings
     with st.phase("Commit acceleration structure"):
         scene, materials, protos = usda.build_world(desc, me, default_material)
@@ -980,6 +996,9 @@ def render_with_report(path, spp=None, out_exr=None, width=None, height=None, ma
                               s["strategy"], s["filter"], s["filter_radius"], float(var), s["min_spp"])
     r = Renderer(scene, materials, desc.lights, make_camera(**desc.camera), settings)
     r._protos = protos
+    vol = usda.build_volumes(desc, me) if volumes else None
+    if vol is not None:
+        r.set_volumes(vol)
     n = int(spp if spp is not None else s["spp"])
     with st.phase("Render"):
         if var > 0:

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/crt.h"
+#include "../../include/crt_render_volumes.h"
 
 namespace crt {
 
@@ -377,7 +378,8 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
 // finds there. A new instance is one row of a list and one line of policy in plan_launches. Plain C++17, no HIP names:
 // tests/test_launch_plan.py sweeps the function on the CPU.
 // ---------------------------------------------------------------------------------------------
-enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC };
+enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC,
+                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME };
 struct InstanceKey {  // a kernel template and its arguments, in the template's order (bools as 0 / 1)
   uint8_t family = KF_NONE;
   uint8_t arg[5] = {0, 0, 0, 0, 0};
@@ -433,6 +435,13 @@ struct InstanceKey {  // a kernel template and its arguments, in the template's 
 #define CRT_INSTANCES_SHADOW(X) /* k_shadow<STATS, WIDE>, k_shadow_curve<STATS>, k_shadow_cubic<STATS> */ \
   X(SHADOW, k_shadow, false, 0) X(SHADOW, k_shadow, false, 1) CRT_WIDE_DIRECT_INSTANCES_SHADOW(X) X(SHADOW, k_shadow, true, 0) X(SHADOW, k_shadow, true, 1) \
   X(SHADOW_CURVE, k_shadow_curve, false) X(SHADOW_CURVE, k_shadow_curve, true) X(SHADOW_CUBIC, k_shadow_cubic, false) X(SHADOW_CUBIC, k_shadow_cubic, true)
+// k_shade_vol<MATS, INF, LIT>: the shade instances of volume renders (PlanInputs::volumes) — three waves, raw material
+// records; INF 0 none / 1 distant lights and uniform domes / 2 mapped domes too. k_volume and k_shadow_volume have one
+// form each: their keys carry the family alone.
+#define CRT_INSTANCES_SHADE_VOL(X) /* k_shade_vol<MATS, INF, LIT> */ \
+  X(SHADE_VOL, k_shade_vol, 0, 0, false) X(SHADE_VOL, k_shade_vol, 0, 0, true) X(SHADE_VOL, k_shade_vol, 0, 1, true) X(SHADE_VOL, k_shade_vol, 0, 2, true) \
+  X(SHADE_VOL, k_shade_vol, 1, 0, false) X(SHADE_VOL, k_shade_vol, 1, 0, true) X(SHADE_VOL, k_shade_vol, 1, 1, true) X(SHADE_VOL, k_shade_vol, 1, 2, true) \
+  X(SHADE_VOL, k_shade_vol, 2, 0, false) X(SHADE_VOL, k_shade_vol, 2, 0, true) X(SHADE_VOL, k_shade_vol, 2, 1, true) X(SHADE_VOL, k_shade_vol, 2, 2, true)
 
 // What the choice of a batch's kernels depends on. The renderer keeps one: the engine choice, the A/B knobs and the
 // build's switches are filled when it is created; what its Params hold, and the per-batch fields, before every plan.
@@ -464,6 +473,10 @@ struct PlanInputs {
   bool cam_compact_ok = true;     // CRT_CAM_COMPACT
   int root_cull_knob = -1;        // CRT_ROOT_CULL: 0 = generate never finishes a camera ray, 1 = wherever the rule allows (A/B, tests)
   float root_miss_share = 0.0f;   // share of a coarse grid of camera rays that misses every child of the root (pathtrace.hip)
+  // A volume aggregate is bound (crt_renderer_set_volumes): the batch runs one launch per stage whatever its size, with
+  // k_volume between extend and shade, the VOL shade instances and — where the shadow stage runs — k_shadow_volume ahead
+  // of k_shadow. false: exactly the plan of a renderer that never heard of volumes.
+  bool volumes = false;
   // per batch
   size_t total = 0;               // paths of the batch
   bool stats = false;             // the stats build (crt_render_samples_stats)
@@ -513,6 +526,10 @@ struct LaunchPlan {
   // The pipelined kernel's launches hand each other the SLIM path state (kernels/pathtrace.hip, PathSoA): three planes,
   // without the words every live path of a launch shares and without the radiance, which is +0 where nothing emits. A
   // field of its own — shade_early names the same instance whatever this says; render_lane launches shade_slim_key().
+  // Volume renders (PlanInputs::volumes): k_volume runs between extend and shade of every bounce, k_shadow_volume ahead
+  // of k_shadow where the shadow stage runs; `shade` then names a KF_SHADE_VOL instance. none = not launched.
+  bool volumes = false;
+  InstanceKey volume_key, shadow_volume_key;
   bool slim_state = false;
   InstanceKey shade_slim_key() const {
     InstanceKey k = slim_state ? shade_early : InstanceKey{};
@@ -538,16 +555,21 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
   pl.fused = q.force_fused >= 0 ? q.force_fused != 0 : !(q.prefer_stage && q.total >= q.stage_min_paths);
   // the stats build is the per-stage one; no fused instance carries the lights at infinity (see k_path) — nor a tail then
   if (q.stats || q.has_inf_lights) pl.fused = false;
+  // Volume renders: always one launch per stage — no fused instance and no tail carries the walk (the general shade
+  // instances sit at their register limit, below; the walk is a kernel of its own between two stages).
+  if (q.volumes) pl.fused = false;
+  pl.volumes = q.volumes;
   const bool stage = !pl.fused, lit = q.n_lights > 0;
   pl.wide = stage && e.wide;  // the fused kernel is a three-wave kernel whatever the scene prefers
   // The TAIL: from bounce `tail_from` on, what is left of the batch — roulette has ended all but a few paths per ten
   // thousand by then (bench: 6.6 M of 531 M rays at bounce 4, 0.1 M at bounce 6) — runs as ONE launch of the fused
   // path-loop kernel over the same segments instead of two or three launches per bounce up to the depth limit (bench,
   // depth 32: 52 launches, ~2 ms of a 137 ms step). Not for the stats build: its kernels count.
-  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights;
+  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights && !q.volumes;
   if (tail) pl.tail_at = (uint32_t)q.tail_from;
   // camera paths as 16-byte records: per-stage launches of an UNLIT scene, pinhole camera, static scene
-  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion) ? 1u : 0u;
+  // (not in a volume render: k_volume reads and rewrites the full form)
+  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion && !q.volumes) ? 1u : 0u;
   // The root cull (generate_segment_cull): per-stage launches of an image whose root is a node, when a camera ray that
   // escapes ends on the sky gradient — a depth limit above 0 and no light at infinity (their escaped rays take the
   // vertex step) — and where the frame shows enough background for it to pay (CRT_ROOT_CULL=1 skips that estimate). Not
@@ -557,7 +579,8 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
   // their register limit (k_shade<2, false, false, false, false> gained three spilled registers with it) and read the
   // full form instead.
   pl.root_cull = q.root_cull_build && q.root_cull_knob != 0 && (q.root_cull_knob > 0 || q.root_miss_share >= kRootCullMinShare) &&
-                 stage && !q.stats && q.scene.root != CRT_INVALID_ID && q.max_depth > 0 && !q.has_inf_lights;
+                 stage && !q.stats && q.scene.root != CRT_INVALID_ID && q.max_depth > 0 && !q.has_inf_lights &&
+                 !q.volumes;  // a ray that misses the root's boxes may still cross a region
   if (pl.root_cull && pl.cam_compact) pl.cam_compact = q.mats_kind == 0 ? 2u : 0u;
   pl.shadow = stage && lit && q.strategy != CRT_STRATEGY_BSDF;
   pl.noclassify_from = q.noclassify_from;
@@ -588,17 +611,22 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
     // when the scene runs the wide kernels), whether the light list is empty; a mapped dome: the instances with its arm
     const bool shade_wide = simple && !q.has_inf_lights && pl.wide && !q.mat_index && q.shade_wide != 0;
     pl.shade = q.has_env ? key(KF_SHADE_ENV, q.mats_kind, drv) : key(KF_SHADE, q.mats_kind, q.has_inf_lights, shade_wide, lit, drv);
-    if (shade_wide && shade_pipe_fits(q) && q.noclassify_from > 0) pl.shade_early = key(KF_SHADE_PIPE, drv);
+    if (q.volumes) {  // the VOL instances: three waves, raw records; neither the pipelined kernel nor the slim state
+      pl.shade = key(KF_SHADE_VOL, q.mats_kind, q.has_env ? 2 : (q.has_inf_lights ? 1 : 0), lit);
+      pl.volume_key = key(KF_VOLUME, 0);
+      if (pl.shadow) pl.shadow_volume_key = key(KF_SHADOW_VOLUME, 0);
+    } else if (shade_wide && shade_pipe_fits(q) && q.noclassify_from > 0) pl.shade_early = key(KF_SHADE_PIPE, drv);
     pl.slim_state = pl.shade_piped() && q.no_emitter && q.slim_state != 0;
     if (pl.shadow) {
       if (e.curve) { pl.shadow_key = key(e.cubic ? KF_SHADOW_CUBIC : KF_SHADOW_CURVE, q.stats); shadow_cold = curve_cold; }
       else pl.shadow_key = key(KF_SHADOW, q.stats, width);
     }
   }
-  const bool ok = (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
+  const bool ok = !(q.volumes && q.stats) &&  // the stats build counts no walk: refused (crt_render_samples_stats)
+                  (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
                   (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = InstanceKey{}; pl.slim_state = false; }
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }
@@ -708,6 +736,10 @@ namespace dev { struct VolRegionRec; }
 struct VolumesView { const dev::VolRegionRec *regions = nullptr; const float *grid = nullptr; uint32_t n_regions = 0; };
 int volumes_build_image(const CrtVolumeRegion *regions, size_t n, const float *grid, size_t grid_len, std::vector<unsigned char> &image);
 int volumes_device(CrtVolumes *v, VolumesView &out);
+// A handle is reference counted: crt_volumes_new hands the caller one reference, crt_volumes_free drops it, a renderer
+// holds one of its own while the aggregate is bound (crt_renderer_set_volumes).
+void volumes_retain(CrtVolumes *v);
+void volumes_release(CrtVolumes *v);
 uint32_t volumes_region_count(const CrtVolumes *v);
 // printf-style text for crt_last_error() on this thread (failures that are not HIP calls).
 void set_error_text(const char *fmt, ...);

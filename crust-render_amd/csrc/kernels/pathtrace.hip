@@ -33,6 +33,7 @@
 
 #include "shade.hip.h"
 #include "traverse_pool.hip.h"
+#include "volume.hip.h"
 
 namespace crt {
 
@@ -52,13 +53,18 @@ namespace {
 #endif
 
 enum { K_CAMERA = 0, K_PATH = 1, K_TIME = 2 };                 // tracer.rs:20-22 (off root)
-enum { K_NEE = 0, K_BSDF = 2, K_PHASE = 4, K_RR = 5, K_MEDIUM = 6 };  // tracer.rs:23-30 (off vertex)
+enum { K_NEE = 0, K_NEE_SHADOW = 1, K_BSDF = 2, K_PHASE = 4, K_RR = 5, K_MEDIUM = 6, K_VOLUME = 7 };  // tracer.rs:23-30 (off vertex)
 constexpr int kRrStartBounce = 3;                              // tracer.rs:46
 constexpr float kRrMinProb = 0.05f;                            // tracer.rs:47
 constexpr uint32_t kFilmTarget = 0x80000000u;
 constexpr uint32_t kPrevValid = 1u << 16, kPrevDelta = 1u << 17;
 constexpr int kMediumShift = 18;             // aux[18:32): 1-based compact id of the interior medium the ray travels in
 constexpr uint32_t kMaxMedia = (1u << 14) - 1;
+// Volume renders (k_volume): a path that scattered inside a region carries one of these four words where its hit record's
+// geometry word was — bit 0: the path survived its roulette, bit 1: the phase vertex asks for a shadow ray. No geometry id
+// reaches them (a material table has fewer than 2^31 - 16 records), and kInvalid (a miss) is none of them.
+constexpr uint32_t kVolScatter = 0xfffffff0u;
+__device__ __forceinline__ bool vol_scatter_word(uint32_t hg) { return hg >= kVolScatter && hg < kVolScatter + 4u; }
 
 // Streaming accesses (path state, hit records, queues, staging film: written once, read once a whole segment pass
 // later — far beyond any cache) carry the non-temporal hint, so they do not push the BVH's nodes, instance records
@@ -108,6 +114,10 @@ struct PathSoA {
                 // n_rec (low 16) + remaining depth (high 16) | sample-in-batch (low 16) + kPrevValid + kPrevDelta
                 // + carried-medium id (high 14)
   float4 *e;    // previous vertex position + previous bounce pdf (PrevBounce, tracer.rs:899-906); lit scenes only
+                // A PHASE previous vertex (PrevVertex::Phase, a scatter inside a volume region: k_volume) needs no bit of
+                // its own: it is kPrevValid without kPrevDelta with e = (p, phase_pdf). The emitter weights read nothing
+                // else of a previous vertex — the material's eval() check of a surface one is already folded into
+                // kPrevDelta (emission_weight below) — so the two kinds are one record here.
   float *time;  // shutter time; scenes with motion only
   // The SLIM form, between two launches of k_shade_pipe<DRV, true> only (LaunchPlan::slim_state: no record of the
   // material table emits, so L is +0 at every vertex; no media, so no carried medium):
@@ -663,12 +673,18 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend(
 #define CRT_SHADE_STAMPS 0
 #endif
 // INF: 0 no light at infinity in the list | 1 distant lights and uniform domes | 2 mapped domes too (k_shade_env)
-template <int MATS, int INF, bool LIT, int ARENA, bool DRV>
+// VOL: the instances of volume renders (k_shade_vol). k_volume has run between extend and this stage: segment transmittance
+// and emission are in beta and L already, and a path that scattered inside a region arrives as a finished phase vertex
+// behind a kVolScatter hit word — its values are loaded into the variables of the tail below, which compacts, queues the
+// shadow request and stages as for any vertex; the vertex code is skipped. Every shadow request's K_NEE_SHADOW seed goes
+// to qseed (k_shadow_volume walks the segment with it).
+template <int MATS, int INF, bool LIT, int ARENA, bool DRV, bool VOL = false>
 __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                               const ShadowSoA &Q, Counters *C, int cur, float4 *staging,
                                               uint32_t *sobol_tab /* ARENA dwords: Sobol tables, then the material table */,
                                               bool first /* camera paths whose plane c was not written (generate_segment) */,
-                                              bool all_pending = false /* no CLASSIFY pass: every path takes the vertex step */) {
+                                              bool all_pending = false /* no CLASSIFY pass: every path takes the vertex step */,
+                                              uint32_t *qseed = nullptr /* VOL: one word per shadow-queue slot */) {
   constexpr bool MEDIA = MATS == 2, SIMPLE = MATS == 0;
   static_assert(SIMPLE || !DRV, "the derived record covers what a simple-material table reads (shade.hip.h)");
   typedef MatTable<DRV> Table;
@@ -810,7 +826,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
           st_nt(&staging[(D.w & 0xffffu) * P.n_act + D.y], make_float4(L.x, L.y, L.z, 0.0f));
         } else {
           pending = true;
-          if (part && hg != kInvalid) {
+          if (part && hg != kInvalid && !(VOL && vol_scatter_word(hg))) {
             const uint32_t g = hg & 0x7fffffffu;
             const uint32_t mi_c = (MAT_INDEX && P.mat_index) ? (uint32_t)P.mat_index[g] : g;
             cls = cls_in_lds ? cls_lds[mi_c] : P.mat_class[mi_c];
@@ -884,7 +900,8 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
       if (MEDIA && med_id) med = P.media_by_id[med_id - 1];
       n_med = med_id;
       const uint32_t hg = H.geom[i];
-      const bool has_hit = hg != kInvalid;
+      const bool vol_vertex = VOL && vol_scatter_word(hg);  // a phase vertex k_volume prepared: no surface, no material
+      const bool has_hit = hg != kInvalid && !vol_vertex;
       const uint32_t geom = hg & 0x7fffffffu;
       // the material record's index: the geometry id, or (deduplicated tables) one 2-byte load away
       const uint32_t mat_i = (MAT_INDEX && has_hit && P.mat_index) ? (uint32_t)P.mat_index[geom] : geom;
@@ -927,7 +944,17 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
         return 1.0f;
       };
 
-      if (remaining <= 0) {  // tracer.rs:1123-1149: depth exhausted, last-vertex emission only
+      if (VOL && vol_vertex) {  // tracer.rs:1192-1249, computed by k_volume (which also counted it): the tail's inputs
+        alive = (hg & 1u) != 0;
+        n_o = ro; n_d = rd; hit_p = ro;  // the new ray leaves the scatter point; beta, L, n_med are what was loaded
+        n_delta = false; n_prev_valid = true;
+        if (LIT) {
+          const float4 E = S.e[i], hq = H.h[i];
+          n_ppdf = E.w;
+          want_shadow = (hg & 2u) != 0;
+          sh_c = v3(E.x, E.y, E.z); sh_d = v3(hq.x, hq.y, hq.z); sh_tmax = hq.w;
+        }
+      } else if (remaining <= 0) {  // tracer.rs:1123-1149: depth exhausted, last-vertex emission only
         s_depth++;
         if (prev_valid) {
           s_closest++;
@@ -1089,6 +1116,8 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
       st_nt(&Q.a[q], make_float4(hit_p.x, hit_p.y, hit_p.z, sh_tmax));
       st_nt(&Q.b[q], make_float4(sh_d.x, sh_d.y, sh_d.z, time));
       st_nt(&Q.c[q], make_float4(sh_c.x, sh_c.y, sh_c.z, __uint_as_float(alive ? j : (kFilmTarget | film_idx))));
+      if (VOL)  // the vertex domain once more (tracer.rs:1121): the shadow segment's walk is seeded off it
+        st_nt(&qseed[q], rng_seed(new_domain(new_domain(Sampler{pattern, P.sample_begin + sl}, (int)(meta & 0xffffu)), K_NEE_SHADOW)));
     }
     lap(5, false);
     __syncthreads();  // every lane has read its ring entry before CLASSIFY appends again
@@ -1127,6 +1156,174 @@ __global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_env(Params P,
                                                                        Counters *C, int cur, float4 *staging, int first) {
   __shared__ uint32_t sobol_tab[kArenaDwords];
   shade_segment<MATS, 2, true, kArenaDwords, DRV>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0);
+}
+
+// The instances of volume renders: three waves, raw material records. INF as shade_segment's: 0 / 1 / 2 (mapped domes).
+template <int MATS, int INF, bool LIT>
+__global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_vol(Params P, PathSoA S, PathSoA N, HitSoA H, ShadowSoA Q,
+                                                                       Counters *C, int cur, float4 *staging, int first, uint32_t *qseed) {
+  static_assert(LIT || !INF, "lights at infinity are lights");
+  __shared__ uint32_t sobol_tab[kArenaDwords];
+  shade_segment<MATS, INF, LIT, kArenaDwords, false, true>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0, qseed);
+}
+
+// ---- volume: the regions a segment crosses (volume.hip.h), between extend and shade of a volume render ----
+// One live path per lane; a lane's spans and lobe weights are LDS columns [region][thread], as in volume_seam.hip. The
+// VOLUME-FORWARD form, per path, with v the vertex domain and seed = rng_seed(new_domain(v, K_VOLUME)):
+//   no region has an active interval on the segment: nothing is touched
+//   depth exhausted (previous vertex valid, surface hit):  beta *= transmittance(ray, 0.001, t_hit)
+//   otherwise:  E = sample_interaction(ray, 0.001, min(t_surf, t_med));  L += beta * E.emitted;  beta *= E.weight
+//     passthrough: beta and L go back to the state; shade's medium, escape and surface arms run on them unchanged
+//     scatter: the phase vertex (tracer.rs:1192-1249) is finished HERE — direction and pdf (K_PHASE), volume_nee
+//       (K_NEE; phase value unclamped, light_weight(light_pdf, phase_val)), roulette on the multiplied beta (K_RR) — and
+//       written over the path: a = p | dir.x, b = dir.yz | beta.xy, c = beta.z | L, e = contribution | phase_pdf, the hit
+//       record = shadow direction | tmax, the hit word = kVolScatter | survived | shadow << 1. Plane d keeps the vertex's
+//       words: shade's tail advances them.
+// A walk that runs into CRT_VOLUME_STEP_LIMIT is the all-zero event (weight 0, emitted 0): the path goes on with beta = 0.
+// first: camera paths, whose plane c generate did not write — it is written here for every path, so shade reads it.
+struct VolArgs { const VolRegionRec *regions; const float *grid; uint32_t n_regions; };
+__global__ __launch_bounds__(kBlock) void k_volume(Params P, PathSoA S, HitSoA H, Counters *C, int cur, int first, VolArgs V) {
+  __shared__ uint32_t sobol_tab[kSobolLdsWords];
+  __shared__ float span_a[kVolMaxRegions][kBlock], span_b[kVolMaxRegions][kBlock], lobe_w[kVolMaxRegions][kBlock];
+  __shared__ uint32_t lds_ctr[8];  // [1..5] statistics, at their RayStats indices
+  __shared__ uint32_t pre[kBins + 1];
+  bins_prefix(&C->seg[cur][blockIdx.x * kBins], pre);
+  const uint32_t n = pre[kBins];
+  if (n == 0) return;  // uniform per workgroup
+  if (threadIdx.x < 8) lds_ctr[threadIdx.x] = 0;
+  sobol_tables_init(sobol_tab);  // ends with a workgroup barrier
+  float *sa = &span_a[0][threadIdx.x], *sb = &span_b[0][threadIdx.x], *lw = &lobe_w[0][threadIdx.x];
+  const uint32_t n_lights = P.n_lights;
+  uint32_t s_closest = 0, s_shadow = 0, s_vertices = 0, s_rr_t = 0, s_rr_k = 0;
+  for (uint32_t k = threadIdx.x; k < n; k += kBlock) {
+    const uint32_t i = bin_slot(k, pre, P.seg_cap);
+    const float4 A = S.a[i], B = S.b[i];
+    const uint4 D = S.d[i];
+    float4 Cc = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    if (!first) Cc = S.c[i];
+    const uint32_t hg = H.geom[i];
+    const bool has_hit = hg != kInvalid;
+    const V3 ro = v3(A.x, A.y, A.z), rd = v3(A.w, B.x, B.y);
+    V3 beta = v3(B.z, B.w, Cc.x), L = v3(Cc.y, Cc.z, Cc.w);
+    const uint32_t pattern = D.x, meta = D.z, aux = D.w;
+    const uint32_t n_rec = meta & 0xffffu;
+    const int remaining = (int)(meta >> 16);
+    const bool prev_valid = (aux & kPrevValid) != 0;
+    const float t_surf = has_hit ? H.h[i].x : CRT_INF;
+    const Sampler vdom = new_domain(Sampler{pattern, P.sample_begin + (aux & 0xffffu)}, (int)n_rec);  // tracer.rs:1121
+    const uint32_t seed = rng_seed(new_domain(vdom, K_VOLUME));
+    bool touched = false;
+    if (remaining <= 0) {  // tracer.rs:1123-1149: the last segment only attenuates what its surface emits
+      if (prev_valid && has_hit) {
+        const VolSpans Sp = vol_active_intervals(V.regions, V.n_regions, ro, rd, 0.001f, t_surf, sa, sb, kBlock);
+        if (Sp.mask != 0u) {
+          V3 tr;
+          (void)vol_transmittance_spans(V.regions, V.n_regions, V.grid, ro, rd, Sp, seed, sa, sb, kBlock, tr);
+          beta = beta * tr;
+          touched = true;
+        }
+      }
+    } else {
+      // the carried medium's free-flight candidate bounds the segment (tracer.rs:1159-1165): a pure function of the
+      // vertex domain, so shade recomputes the same value
+      float t_med = CRT_INF;
+      const uint32_t med_id = aux >> kMediumShift;
+      if (med_id) {
+        const DevMedium med = P.media_by_id[med_id - 1];
+        if (med.present && med.scattering) t_med = -(log_det(draw_rnd1(new_domain(vdom, K_MEDIUM)))) / med.sigma_bar;
+      }
+      const float t_end = t_med < t_surf ? t_med : t_surf;  // t_surf.min(t_med)
+      const VolSpans Sp = vol_active_intervals(V.regions, V.n_regions, ro, rd, 0.001f, t_end, sa, sb, kBlock);
+      if (Sp.mask != 0u) {
+        const VolEvent E = vol_sample_interaction_spans(V.regions, V.n_regions, V.grid, ro, rd, Sp, seed, sa, sb, lw, kBlock);
+        L = L + beta * E.emitted;
+        beta = beta * E.weight;
+        touched = true;
+        if (E.kind == CRT_VOLUME_SCATTER) {  // === the phase vertex (tracer.rs:1192-1249) ===
+          s_closest++;  // this iteration's World::intersect (tracer.rs:1152): shade skips the vertex it is counted in
+          const V3 wi = normalize(rd);
+          float ps[4];
+          draw_sample4(new_domain(vdom, K_PHASE), ps, sobol_tab);
+          V3 dir;
+          float phase_pdf;
+          vol_phase_sample(V.regions, V.n_regions, E, lw, kBlock, rd, ps[0], ps[1], ps[2], dir, phase_pdf);
+          // volume_nee (tracer.rs:1040-1076)
+          bool want_shadow = false;
+          V3 sh_d = splat(0.0f), sh_c = splat(0.0f);
+          float sh_tmax = 0.0f;
+          if (P.strategy != CRT_STRATEGY_BSDF && n_lights > 0) {
+            float nee_s[4];
+            draw_sample4(new_domain(vdom, K_NEE), nee_s, sobol_tab);
+            uint32_t li = (uint32_t)(nee_s[0] * (float)n_lights);  // LightList::pick, light.rs:421-429
+            if (li > n_lights - 1) li = n_lights - 1;
+            LightSample ls;
+            if (light_sample_li_env<2>(P.lights[li], P.envs, E.p, nee_s[1], nee_s[2], ls)) {
+              s_shadow++;
+              want_shadow = true;
+              sh_d = ls.direction;
+              sh_tmax = ls.distance - 0.001f;
+              const float phase_val = vol_phase_pdf(V.regions, V.n_regions, E, lw, kBlock, dot(wi, ls.direction));
+              const float light_pdf = rmax(ls.pdf / (float)n_lights, 1e-6f);
+              const V3 c = ((ls.radiance * phase_val) * light_weight(P.strategy, light_pdf, phase_val)) / light_pdf;
+              sh_c = beta * c;
+            }
+          }
+          bool survived = true;
+          if (n_rec >= (uint32_t)kRrStartBounce) {
+            s_rr_t++;
+            const float p_survive = rclamp(max_elem(beta), kRrMinProb, 1.0f);
+            if (p_survive < 1.0f) {
+              if (draw_rnd1(new_domain(vdom, K_RR)) >= p_survive) {
+                survived = false;
+                s_rr_k++;
+              } else {
+                beta = beta / p_survive;
+              }
+            }
+          }
+          s_vertices++;
+          S.a[i] = make_float4(E.p.x, E.p.y, E.p.z, dir.x);
+          S.b[i] = make_float4(dir.y, dir.z, beta.x, beta.y);
+          if (n_lights) {
+            S.e[i] = make_float4(sh_c.x, sh_c.y, sh_c.z, phase_pdf);
+            H.h[i] = make_float4(sh_d.x, sh_d.y, sh_d.z, sh_tmax);
+          }
+          H.geom[i] = kVolScatter | (survived ? 1u : 0u) | (want_shadow ? 2u : 0u);
+        } else {
+          S.b[i] = make_float4(B.x, B.y, beta.x, beta.y);
+        }
+      }
+    }
+    if (remaining <= 0 && touched) S.b[i] = make_float4(B.x, B.y, beta.x, beta.y);
+    if (touched || first) S.c[i] = make_float4(beta.z, L.x, L.y, L.z);
+  }
+  add_stat(&lds_ctr[1], s_closest); add_stat(&lds_ctr[2], s_shadow); add_stat(&lds_ctr[3], s_vertices);
+  add_stat(&lds_ctr[4], s_rr_t); add_stat(&lds_ctr[5], s_rr_k);
+  __syncthreads();
+  if (threadIdx.x >= 1 && threadIdx.x <= 5 && lds_ctr[threadIdx.x])
+    atomicAdd(&C->stats[threadIdx.x], (unsigned long long)lds_ctr[threadIdx.x]);
+}
+
+// ---- shadow, volume renders: every request's contribution times the transmittance of its segment, before k_shadow pays
+// the unoccluded ones out (the product is the last operation on the contribution: DESIGN.md §2). One request per lane;
+// occluded requests are walked too. ----
+__global__ __launch_bounds__(kBlock) void k_shadow_volume(Params P, ShadowSoA Q, const uint32_t *qseed, Counters *C, VolArgs V) {
+  __shared__ float span_a[kVolMaxRegions][kBlock], span_b[kVolMaxRegions][kBlock];
+  const uint32_t n = ((const volatile uint32_t *)C->shadow)[blockIdx.x];
+  const uint32_t seg0 = blockIdx.x * P.seg_cap;
+  float *sa = &span_a[0][threadIdx.x], *sb = &span_b[0][threadIdx.x];
+  for (uint32_t k = threadIdx.x; k < n; k += kBlock) {  // n <= seg_cap: shade appended them
+    const uint32_t q = seg0 + k;
+    const float4 A = Q.a[q], B = Q.b[q];
+    const V3 ro = v3(A.x, A.y, A.z), rd = v3(B.x, B.y, B.z);
+    const VolSpans Sp = vol_active_intervals(V.regions, V.n_regions, ro, rd, 0.001f, A.w, sa, sb, kBlock);
+    if (Sp.mask == 0u) continue;
+    V3 tr;
+    (void)vol_transmittance_spans(V.regions, V.n_regions, V.grid, ro, rd, Sp, qseed[q], sa, sb, kBlock, tr);
+    float4 Cc = Q.c[q];
+    Cc.x = Cc.x * tr.x; Cc.y = Cc.y * tr.y; Cc.z = Cc.z * tr.z;
+    Q.c[q] = Cc;
+  }
 }
 
 // ---- shade, PIPELINED: the four-wave kernel of unlit simple-material scenes with one material class (cornellbox, the
@@ -1682,6 +1879,7 @@ using PathFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *,
 using ShadeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int);
 using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int, uint32_t, int);
 using ShadowFn = void (*)(Params, PathSoA, ShadowSoA, Counters *, float4 *, CrtTravStats *);
+using ShadeVolFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, uint32_t *);
 template <class Fn>
 struct InstanceRow { InstanceKey key; Fn fn; };
 #define CRT_ROW(family, kernel, ...) {CRT_INSTANCE_KEY(family, kernel, __VA_ARGS__), kernel<__VA_ARGS__>},
@@ -1690,6 +1888,7 @@ static const InstanceRow<PathFn> kPathRows[] = {CRT_INSTANCES_PATH(CRT_ROW)};
 static const InstanceRow<ShadeFn> kShadeRows[] = {CRT_INSTANCES_SHADE(CRT_ROW)};
 static const InstanceRow<ShadePipeFn> kShadePipeRows[] = {CRT_INSTANCES_SHADE_PIPE(CRT_ROW) CRT_INSTANCES_SHADE_PIPE_SLIM(CRT_ROW)};
 static const InstanceRow<ShadowFn> kShadowRows[] = {CRT_INSTANCES_SHADOW(CRT_ROW)};
+static const InstanceRow<ShadeVolFn> kShadeVolRows[] = {CRT_INSTANCES_SHADE_VOL(CRT_ROW)};
 #undef CRT_ROW
 // The kernel a key names (nullptr for the empty key: nothing to launch); false when the build holds no such instance.
 template <class Fn, size_t N>
@@ -1723,6 +1922,7 @@ struct Renderer {
     PathSoA S[2]{};
     HitSoA H{};
     ShadowSoA Q{};
+    uint32_t *qseed = nullptr;     // volume renders of lit scenes: the K_NEE_SHADOW seed of every shadow-queue slot
     Counters *C = nullptr;
     float4 *staging = nullptr;
     hipStream_t stream = nullptr;  // lanes 1.. only (lane 0 runs on the caller's stream)
@@ -1752,6 +1952,10 @@ struct Renderer {
   // plan's keys. last_plan: what the LAST batch ran (crt_renderer_pipeline); until the first, the scene's preference.
   PlanInputs in;
   LaunchPlan last_plan;
+  // The bound volume aggregate (crt_renderer_set_volumes): a reference of the renderer's own, and its device image as the
+  // kernels take it. nullptr: none — every batch then runs what it ran before volumes existed.
+  CrtVolumes *volumes = nullptr;
+  VolArgs vol{nullptr, nullptr, 0};
   // What the root cull can save grows with the share of the frame that shows background; what it costs does not:
   // generate's slab tests and compaction, plane d beside the compact form. So the renderer looks first: the root step of
   // the pixel-centre rays of a 32 x 18 grid over the frame, through the lens centre, on the host (at creation), and
@@ -1797,6 +2001,7 @@ struct Renderer {
       if (B.done) (void)hipEventDestroy(B.done);
     }
     if (ev_start) (void)hipEventDestroy(ev_start);
+    volumes_release(volumes);  // behind the synchronised lanes; the caller's stream is the caller's to drain (as for the scene)
     if (film) (void)hipFree(film);
     if (d_materials) (void)hipFree(d_materials);
     if (d_mat_derived) (void)hipFree(d_mat_derived);
@@ -1856,8 +2061,9 @@ struct Renderer {
     const size_t p16 = (cap * 16 + 255) & ~size_t(255);
     const size_t b16 = (bcap * 16 + 255) & ~size_t(255), b4 = (bcap * 4 + 255) & ~size_t(255);
     const bool lit = P.n_lights > 0, motion = P.has_motion != 0;
-    // 2 x (a b c d [e] [16 B] + [time 4 B]) + hit (16 + 4) + shadow 3 x 16 + staging 16
-    blob_bytes = 2 * ((lit ? 5 : 4) * b16 + (motion ? b4 : 0)) + (b16 + b4) + (lit ? 3 * p16 : 0) + p16;
+    const size_t p4 = (lit && volumes) ? ((cap * 4 + 255) & ~size_t(255)) : 0;  // the shadow queue's seed plane (set_volumes frees the blobs)
+    // 2 x (a b c d [e] [16 B] + [time 4 B]) + hit (16 + 4) + shadow 3 x 16 [+ 4] + staging 16
+    blob_bytes = 2 * ((lit ? 5 : 4) * b16 + (motion ? b4 : 0)) + (b16 + b4) + (lit ? 3 * p16 : 0) + p4 + p16;
     // CRT_MAX_BATCH_SLOTS (tests): a batch of more slots asks for more memory than any device has, so the allocation
     // fails the way it does on a part with too little free HBM (bench.py halves the batch then).
     const size_t want_bytes = (max_batch_slots && slots > max_batch_slots) ? ((size_t)1 << 46) : blob_bytes;
@@ -1878,6 +2084,7 @@ struct Renderer {
     }
     H.h = (float4 *)take(b16); H.geom = (uint32_t *)take(b4);
     if (lit) { Q.a = (float4 *)take(p16); Q.b = (float4 *)take(p16); Q.c = (float4 *)take(p16); }
+    B.qseed = p4 ? (uint32_t *)take(p4) : nullptr;
     staging = (float4 *)take(p16);
     cap_slots = cap;
     return CRT_OK;
@@ -1974,6 +2181,11 @@ struct Renderer {
     in.has_motion = P.has_motion != 0; in.lens = P.camera.lens_radius > 0.0f;
     in.mat_index = P.mat_index != nullptr; in.partition = P.partition; in.n_materials = P.n_materials; in.max_depth = P.max_depth;
     in.class_stats = P.class_stats;
+    in.volumes = volumes != nullptr;
+    if (in.volumes && stats) {
+      set_error_text("render refused: the stats build does not run volume renders");
+      return CRT_ERR_UNSUPPORTED;
+    }
     if (plan_launches(in, last_plan) != CRT_OK) {
       set_error_text("render refused: the selected kernels (wide %d, cold %d / %d) cannot run this image (direct words %u, cold %u)",
                      (int)last_plan.wide, last_plan.ext_cold, last_plan.path_cold, P.scene.direct_leaves, P.scene.cold);
@@ -2010,8 +2222,11 @@ struct Renderer {
     ShadeFn shade;
     ShadePipeFn shade_pipe, shade_slim;
     ShadowFn shadow;
+    ShadeVolFn shade_vol = nullptr;
+    if (plan.volumes && !find_instance(kShadeVolRows, plan.shade, shade_vol)) return CRT_ERR_UNSUPPORTED;
+    if (plan.volumes != (volumes != nullptr) || (plan.volumes && (plan.volume_key.none() || plan.fused))) return CRT_ERR_UNSUPPORTED;
     if (!find_instance(kPathRows, plan.path, path) || !find_instance(kExtendRows, plan.extend, extend) ||
-        !find_instance(kShadeRows, plan.shade, shade) || !find_instance(kShadePipeRows, plan.shade_early, shade_pipe) ||
+        (!plan.volumes && !find_instance(kShadeRows, plan.shade, shade)) || !find_instance(kShadePipeRows, plan.shade_early, shade_pipe) ||
         !find_instance(kShadePipeRows, plan.shade_slim_key(), shade_slim) ||
         !find_instance(kShadowRows, plan.shadow_key, shadow))
       return CRT_ERR_UNSUPPORTED;
@@ -2048,7 +2263,12 @@ struct Renderer {
       }
       const int first = it == 0 ? 1 : 0;
       timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
-      if (shade_pipe && (int)it < plan.noclassify_from) {  // the pipelined instance (shade_segment_pipe)
+      if (plan.volumes) {  // the walk, then the VOL shade instance (plane c is k_volume's to write: never `first`), then the shadow segments' walk
+        timed(3, st, [&] { hipLaunchKernelGGL(k_volume, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, vol); });
+        timed(1, st, [&] { hipLaunchKernelGGL(shade_vol, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (int)it >= plan.noclassify_from ? 2 : 0, B.qseed); });
+        if (!plan.shadow_volume_key.none())
+          timed(3, st, [&] { hipLaunchKernelGGL(k_shadow_volume, dim3(grid), dim3(kBlock), 0, st, p, Q, (const uint32_t *)B.qseed, C, vol); });
+      } else if (shade_pipe && (int)it < plan.noclassify_from) {  // the pipelined instance (shade_segment_pipe)
         // Slim state (plan.slim_state): the launch writes the full form where the next consumer of its output is not
         // this kernel again — the tail, the plain k_shade from noclassify_from, or nothing past the depth limit.
         const uint32_t nx = it + 1;
@@ -2316,9 +2536,44 @@ int crt_render_samples(CrtRenderer *r, uint32_t sample_begin, uint32_t sample_co
   if (!r) return CRT_ERR_BAD_ARG;
   return abi_guard("crt_render_samples", [&] { return r->r.render(sample_begin, sample_count, (hipStream_t)stream, nullptr); });
 }
+// k_volume reads planes a, b and d of camera paths; a CRT_REGEN_FIRST build writes no plane d for them (generate_segment)
+// and has shade work them out again, so that A/B build renders no volumes — as it builds neither the root cull nor the
+// pipelined shade kernel.
+constexpr bool kVolumeRenderBuild = !kRegenFirst;
+static int renderer_set_volumes(CrtRenderer *r, CrtVolumes *v) {
+  Renderer &R = r->r;
+  if (v == R.volumes) return CRT_OK;
+  if (v && !kVolumeRenderBuild) {
+    set_error_text("crt_renderer_set_volumes: a CRT_REGEN_FIRST build holds no volume stage");
+    return CRT_ERR_UNSUPPORTED;
+  }
+  VolumesView view;
+  if (v) {  // the image is uploaded here, not by the first batch
+    const int rc = volumes_device(v, view);
+    if (rc != CRT_OK) return rc;
+  }
+  // nothing of an earlier batch may be in flight when the buffers change shape (the seed plane comes and goes with the
+  // binding) or the old aggregate's last reference goes
+  if (!CRT_HIP_OK(hipStreamSynchronize(R.last_stream))) return CRT_ERR_NO_DEVICE;
+  for (Renderer::Lane &B : R.lanes) {
+    if (B.stream) (void)hipStreamSynchronize(B.stream);
+    if (B.blob) (void)hipFree(B.blob);
+    B.blob = nullptr; B.cap_slots = 0; B.blob_bytes = 0; B.qseed = nullptr;
+  }
+  volumes_retain(v);
+  volumes_release(R.volumes);
+  R.volumes = v;
+  R.vol = VolArgs{view.regions, view.grid, view.n_regions};
+  return CRT_OK;
+}
+int crt_renderer_set_volumes(CrtRenderer *r, CrtVolumes *v) {
+  if (!r) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_renderer_set_volumes", [&] { return renderer_set_volumes(r, v); });  // nothing unwinds through the ABI
+}
 int crt_render_samples_stats(CrtRenderer *r, uint32_t sample_begin, uint32_t sample_count, void *stream,
                              CrtTravStats host_stats[2]) {
   if (!r || !host_stats) return CRT_ERR_BAD_ARG;
+  if (r->r.volumes) { set_error_text("crt_render_samples_stats: the stats build does not run volume renders"); return CRT_ERR_UNSUPPORTED; }
   CrtTravStats *d = nullptr;
   if (!CRT_HIP_OK(hipMalloc(&d, 2 * sizeof(CrtTravStats)))) return CRT_ERR_NO_DEVICE;
   (void)hipMemsetAsync(d, 0, 2 * sizeof(CrtTravStats), (hipStream_t)stream);
@@ -2420,7 +2675,8 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   if (!r || !out) return CRT_ERR_BAD_ARG;
   const LaunchPlan &plan = r->r.last_plan;  // every bit below is a per-stage one: plan_launches sets none of them on a fused plan
   out[0] = plan.fused ? 1u : 0u;
-  out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u);
+  out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u) |
+           (plan.volumes ? 16u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

@@ -94,6 +94,10 @@ __device__ __forceinline__ void draw_sample4(Sampler s, float out[4], const uint
 __device__ __forceinline__ float draw_rnd1(Sampler s) {
   return unit_f32(pcg_hash(s.pattern ^ (s.index * 0x9e3779b9u + 0x7f4a7c15u)));
 }
+// domain.rng(): the seed of a free-path walk (volume.hip.h, vol_next_f32) drawn off a domain — the word draw_rnd1 hashes,
+// so the walk's first number IS the domain's draw_rnd1 and, like it, differs from sample to sample of a pixel. (The
+// domain's pattern alone does not: every sample of a pixel would repeat the same walk.)
+__device__ __forceinline__ uint32_t rng_seed(Sampler s) { return s.pattern ^ (s.index * 0x9e3779b9u + 0x7f4a7c15u); }
 
 }  // namespace dev
 }  // namespace crt

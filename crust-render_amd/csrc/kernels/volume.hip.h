@@ -246,11 +246,11 @@ __device__ __forceinline__ VolSpans vol_active_intervals(const VolRegionRec *__r
   return S;
 }
 
-// Volumes::transmittance (volume.rs:492-536). Returns the status; tr = 0 on CRT_VOLUME_STEP_LIMIT.
-__device__ __forceinline__ uint32_t vol_transmittance(const VolRegionRec *__restrict__ regions, uint32_t n_regions,
-                                                      const float *__restrict__ grid, V3 ro, V3 rd, float t_eps, float t_max,
-                                                      uint32_t seed, float *sa, float *sb, uint32_t stride, V3 &tr) {
-  const VolSpans S = vol_active_intervals(regions, n_regions, ro, rd, t_eps, t_max, sa, sb, stride);
+// The walk of Volumes::transmittance over spans the caller already holds (S and the columns vol_active_intervals filled):
+// the renderer's kernels look at S.mask first and touch nothing where no region is crossed.
+__device__ __forceinline__ uint32_t vol_transmittance_spans(const VolRegionRec *__restrict__ regions, uint32_t n_regions,
+                                                            const float *__restrict__ grid, V3 ro, V3 rd, const VolSpans &S,
+                                                            uint32_t seed, const float *sa, const float *sb, uint32_t stride, V3 &tr) {
   tr = splat(1.0f);
   if (S.mask == 0u || S.majorant <= 0.0f) return CRT_VOLUME_OK;
   if (S.hetero == 0u) {  // every crossed region homogeneous: the analytic product
@@ -285,21 +285,28 @@ __device__ __forceinline__ uint32_t vol_transmittance(const VolRegionRec *__rest
   return CRT_VOLUME_STEP_LIMIT;
 }
 
+// Volumes::transmittance (volume.rs:492-536). Returns the status; tr = 0 on CRT_VOLUME_STEP_LIMIT.
+__device__ __forceinline__ uint32_t vol_transmittance(const VolRegionRec *__restrict__ regions, uint32_t n_regions,
+                                                      const float *__restrict__ grid, V3 ro, V3 rd, float t_eps, float t_max,
+                                                      uint32_t seed, float *sa, float *sb, uint32_t stride, V3 &tr) {
+  const VolSpans S = vol_active_intervals(regions, n_regions, ro, rd, t_eps, t_max, sa, sb, stride);
+  return vol_transmittance_spans(regions, n_regions, grid, ro, rd, S, seed, sa, sb, stride, tr);
+}
+
 struct VolEvent {
   uint32_t kind, status, n_lobes, lobe_mask;  // lobe_mask bit r: region r contributed a lobe, its normalised weight in lw[r * stride]
   float t;
   V3 p, weight, emitted;  // weight: the scatter's path weight, or the passthrough's transmittance
 };
 
-// Volumes::sample_interaction (volume.rs:409-486)
-__device__ __forceinline__ VolEvent vol_sample_interaction(const VolRegionRec *__restrict__ regions, uint32_t n_regions,
-                                                           const float *__restrict__ grid, V3 ro, V3 rd, float t_eps, float t_max,
-                                                           uint32_t seed, float *sa, float *sb, float *lw, uint32_t stride) {
+// The walk of Volumes::sample_interaction over spans the caller already holds (see vol_transmittance_spans).
+__device__ __forceinline__ VolEvent vol_sample_interaction_spans(const VolRegionRec *__restrict__ regions, uint32_t n_regions,
+                                                                 const float *__restrict__ grid, V3 ro, V3 rd, const VolSpans &S,
+                                                                 uint32_t seed, const float *sa, const float *sb, float *lw, uint32_t stride) {
   VolEvent E;
   E.kind = CRT_VOLUME_PASSTHROUGH; E.status = CRT_VOLUME_OK; E.n_lobes = 0u; E.lobe_mask = 0u;
   E.t = 0.0f;
   E.p = splat(0.0f); E.weight = splat(1.0f); E.emitted = splat(0.0f);
-  const VolSpans S = vol_active_intervals(regions, n_regions, ro, rd, t_eps, t_max, sa, sb, stride);
   if (S.mask == 0u || S.majorant <= 0.0f) return E;
   const float majorant = S.majorant;
   float t = S.start;
@@ -347,6 +354,14 @@ __device__ __forceinline__ VolEvent vol_sample_interaction(const VolRegionRec *_
   return E;
 }
 
+// Volumes::sample_interaction (volume.rs:409-486)
+__device__ __forceinline__ VolEvent vol_sample_interaction(const VolRegionRec *__restrict__ regions, uint32_t n_regions,
+                                                           const float *__restrict__ grid, V3 ro, V3 rd, float t_eps, float t_max,
+                                                           uint32_t seed, float *sa, float *sb, float *lw, uint32_t stride) {
+  const VolSpans S = vol_active_intervals(regions, n_regions, ro, rd, t_eps, t_max, sa, sb, stride);
+  return vol_sample_interaction_spans(regions, n_regions, grid, ro, rd, S, seed, sa, sb, lw, stride);
+}
+
 __device__ __forceinline__ float vol_hg_phase(float cos_theta, float g) {  // medium.rs:148-152
   const float denom = rmax(1.0f + g * g - 2.0f * g * cos_theta, 1e-6f);
   return (1.0f - g * g) / (4.0f * CRT_PI * denom * sqrtf(denom));
@@ -374,6 +389,16 @@ __device__ __forceinline__ void vol_phase_sample(const VolRegionRec *__restrict_
   for (uint32_t r = 0; r < n_regions; r++)
     if ((E.lobe_mask >> r) & 1u) sum += lw[r * stride] * vol_hg_phase(c, regions[r].g);
   pdf = rmax(sum, 1e-6f);
+}
+
+// PhaseMix::pdf (volume.rs:319-324) of a scatter's lobes at cos_theta, unclamped: the phase value volume_nee weighs a
+// light sample with (tracer.rs:1054-1062).
+__device__ __forceinline__ float vol_phase_pdf(const VolRegionRec *__restrict__ regions, uint32_t n_regions, const VolEvent &E,
+                                               const float *lw, uint32_t stride, float cos_theta) {
+  float sum = 0.0f;
+  for (uint32_t r = 0; r < n_regions; r++)
+    if ((E.lobe_mask >> r) & 1u) sum += lw[r * stride] * vol_hg_phase(cos_theta, regions[r].g);
+  return sum;
 }
 
 }  // namespace dev

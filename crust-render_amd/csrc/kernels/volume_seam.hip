@@ -6,7 +6,8 @@
 // vectors. The region records arrive through a const __restrict__ kernel argument and are indexed by the uniform region
 // loop (scalar loads); a lane's spans and lobe weights are LDS columns [region][thread] — 24 KB a block in the sample
 // kernel, 16 KB in the transmittance kernel — because a runtime-indexed private array would live in scratch
-// (profiles/volume_isa_resources.txt has the rows). The wavefront renderer does not call these yet.
+// (profiles/volume_isa_resources.txt has the rows). The wavefront renderer runs the same header in kernels of its own
+// (pathtrace.hip: k_volume, k_shadow_volume), not these.
 // Compile with -ffp-contract=off (dmath.hip.h).
 #include "volume.hip.h"
 #include "../crt_internal.h"

@@ -137,7 +137,7 @@ struct Volumes {
 
 }  // namespace crt
 
-struct CrtVolumes { std::shared_ptr<crt::Volumes> p; };
+struct CrtVolumes { std::shared_ptr<crt::Volumes> p; std::atomic<int> refs{1}; };
 
 namespace crt {
 
@@ -160,6 +160,9 @@ int volumes_device(CrtVolumes *v, VolumesView &out) {
 
 uint32_t volumes_region_count(const CrtVolumes *v) { return v->p->n_regions; }
 
+void volumes_retain(CrtVolumes *v) { if (v) v->refs.fetch_add(1, std::memory_order_relaxed); }
+void volumes_release(CrtVolumes *v) { if (v && v->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete v; }
+
 }  // namespace crt
 
 using namespace crt;
@@ -181,7 +184,7 @@ CrtVolumes *crt_volumes_new(const CrtVolumeRegion *regions, size_t n, const floa
   return out;
 }
 
-void crt_volumes_free(CrtVolumes *v) { delete v; }
+void crt_volumes_free(CrtVolumes *v) { volumes_release(v); }
 
 int crt_volumes_image(const CrtVolumes *v, const void **image, size_t *bytes) {
   if (!v || !image || !bytes) return CRT_ERR_BAD_ARG;

@@ -265,7 +265,8 @@ def for_render(scene, renderer, spp, stats=None):
     st.scene = SceneCounters(geometries=scene.geometry_count(),
                              top_level=PrimitiveCounts(**scene.primitive_breakdown()),
                              unique=PrimitiveCounts(**scene.unique_primitive_breakdown()),
-                             lights=renderer.n_lights, volumes=0, footprint=scene.memory_footprint())
+                             lights=renderer.n_lights, volumes=renderer.volumes.n if renderer.volumes is not None else 0,
+                             footprint=scene.memory_footprint())
     s = renderer.settings
     st.image = ImageCounters(s.width, s.height, int(spp), s.max_depth)
     st.rays = RayStats.of(renderer.stats())

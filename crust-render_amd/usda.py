@@ -1121,7 +1121,8 @@ def fill_material(m, overrides):
 
 def build_volumes(desc, api):
     """The aggregate of a description's volume regions (api.volumes.Volumes), or None when it holds none. build_world
-    never calls this: the wavefront renderer does not read volumes yet."""
+    never calls this (regions are no geometry): the caller binds the aggregate with Renderer.set_volumes, as
+    render_with_report(..., volumes=True) does."""
     if not desc.volumes:
         return None
     keys = set(api.volumes.region())

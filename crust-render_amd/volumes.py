@@ -4,7 +4,8 @@ crt_volumes_transmittance_n, crt_volumes_sample_n).
 
 A host integrator that keeps its own trace_path (tracer.rs:1167-1254) calls Scene.intersect_n / occluded_n for the kernel
 seam, shading.py for the per-hit shading and these for fog and smoke: `sample` at every path segment, `transmittance` on
-shadow rays. The wavefront renderer does not read volumes yet. Query and result records live in HBM as torch uint8
+shadow rays. The wavefront renderer runs the same functions itself once an aggregate is bound to it
+(Renderer.set_volumes). Query and result records live in HBM as torch uint8
 tensors; numpy structured dtypes give them field names on the host. There is no CPU fallback: density, transmittance and
 sample launch kernels of libcrt_amd.so. Building the aggregate and reading its image need no device.
 """

@@ -457,7 +457,9 @@ int crt_renderer_shade_class_stats(CrtRenderer *r, int enable, uint64_t out_wave
  * trees and, in the renderer, large ones; crt_scene_engine_select), | 2 when the shade launches were the pipelined
  * four-wave instance (unlit simple-material scenes of one material class whose material table fits its LDS arena beside
  * the staging blocks; CRT_SHADE_PIPE=0: never), | 8 when those launches handed each other the slim 48-byte path state
- * (a material table in which nothing emits; CRT_SLIM_STATE=0: never); out[2] = workgroups (= queue segments) per launch.
+ * (a material table in which nothing emits; CRT_SLIM_STATE=0: never), | 16 when the batch was a volume render (an
+ * aggregate bound with crt_renderer_set_volumes: the volume stage ran between extend and shade of every bounce);
+ * out[2] = workgroups (= queue segments) per launch.
  * The renderer takes the per-stage form for batches of >= 96 Mi paths and the fused kernel for smaller ones and for the
  * tail of a large one. Environment CRT_FUSED / CRT_WIDE / CRT_STAGE_MIN_PATHS / CRT_GRID_MULT override. */
 int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]);
@@ -474,12 +476,15 @@ int crt_renderer_lanes(const CrtRenderer *r);
 int crt_renderer_set_lanes(CrtRenderer *r, int lanes);
 /* Live HIP-event timing of the kernels launched by crt_render_samples since the last reset, by class:
  * 0 = extend (closest-hit traversal) — or, in the fused pipeline, the path-loop kernel that runs generate, extend,
- * shade and shadow of a whole batch in one launch — 1 = shade, 2 = shadow (occlusion traversal), 3 = other.
+ * shade and shadow of a whole batch in one launch — 1 = shade, 2 = shadow (occlusion traversal), 3 = other (generate, the
+ * film fold, the tail and, in a volume render, the two volume kernels: the walk between extend and shade and the walk of
+ * the shadow segments).
  * out_ms[k] = summed duration, out_launches[k] = launches. Enabled by crt_renderer_profile(r, 1). */
 int crt_renderer_profile(CrtRenderer *r, int enable);
 int crt_renderer_profile_read(CrtRenderer *r, double out_ms[4], uint64_t out_launches[4]);
 /* Traversal counters for one batch, from the stats build of the kernels: host_stats[0] += the extend
- * (closest-hit) launches, host_stats[1] += the shadow (any-hit) launches. Synchronises the stream. */
+ * (closest-hit) launches, host_stats[1] += the shadow (any-hit) launches. Synchronises the stream.
+ * CRT_ERR_UNSUPPORTED while a volume aggregate is bound (crt_renderer_set_volumes): the stats build holds no volume stage. */
 int crt_render_samples_stats(CrtRenderer *r, uint32_t sample_begin, uint32_t sample_count, void *stream,
                              CrtTravStats host_stats[2]);
 
@@ -488,7 +493,8 @@ int crt_render_samples_stats(CrtRenderer *r, uint32_t sample_begin, uint32_t sam
  * oriented box (a 3x4 placement applied to [-half, half]^3) filled with a density field; the aggregate samples one
  * interaction along a segment (weighted delta tracking, Volumes::sample_interaction, volume.rs:409-486) and estimates
  * transmittance (analytic when every crossed region is homogeneous, ratio tracking otherwise, volume.rs:492-536).
- * The wavefront renderer does not read volumes yet. Departures from the reference:
+ * The wavefront renderer reads an aggregate bound with crt_renderer_set_volumes (crt_render_volumes.h) through the same functions.
+ * Departures from the reference:
  *  - a walk is bounded: after CRT_VOLUME_MAX_STEPS collision candidates it stops with status CRT_VOLUME_STEP_LIMIT and
  *    an all-zero result (the reference loops for ever on a NaN distance or an infinite segment);
  *  - at most CRT_VOLUME_MAX_REGIONS regions per aggregate (also the lobe capacity of a scatter record) and
@@ -554,7 +560,9 @@ typedef struct CrtVolumes CrtVolumes;
  * field of a record, an unknown field kind, more than CRT_VOLUME_MAX_OCTAVES octaves, grid dims whose product is 0 or
  * is not grid_count, a grid range outside the array, a placement without a finite inverse. */
 CrtVolumes *crt_volumes_new(const CrtVolumeRegion *regions, size_t n, const float *grid, size_t grid_len);
+/* Drops the caller's reference; a renderer the aggregate is bound to keeps it alive until it is detached or freed. */
 void crt_volumes_free(CrtVolumes *v);
+/* Binding an aggregate to a CrtRenderer (volume renders): crt_render_volumes.h. */
 /* The image the kernels read (host memory, owned by the handle): a 256-byte header, the region records, the grid data. */
 int crt_volumes_image(const CrtVolumes *v, const void **image, size_t *bytes);
 /* VolumeRegion::density (volume.rs:234-242) of region `region` at n world points (3 floats each). */
