@@ -183,6 +183,8 @@ ABI_SYMBOLS = [
 # include/crt_render_volumes.h: the entry point of volume renders, declared beside crt.h (whose 84 declarations the list
 # above mirrors) and exported by the same library.
 ABI_SYMBOLS_RENDER_VOLUMES = ["crt_renderer_set_volumes"]
+# include/crt_scene_image.h: the host-only hand-out of the scene image's arrays, declared beside crt.h for the same reason.
+ABI_SYMBOLS_SCENE_IMAGE = ["crt_scene_image_array"]
 
 _lib = None
 
@@ -239,6 +241,8 @@ def lib():
         L.crt_scene_image_check.argtypes = [vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "crt_scene_image_prims"):  # absent from older A/B variant libraries
         L.crt_scene_image_prims.argtypes = [vp, up, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "crt_scene_image_array"):  # absent from older A/B variant libraries
+        L.crt_scene_image_array.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), up]
     if hasattr(L, "crt_scene_root_touched_n"):  # absent from older A/B variant libraries
         L.crt_scene_root_touched_n.argtypes = [vp, fp, C.c_size_t, C.c_float, C.c_float, C.POINTER(C.c_uint8), up]
     if hasattr(L, "crt_scene_engine_select"):  # absent from older A/B variant libraries
@@ -454,6 +458,24 @@ class Scene:
             _check(lib().crt_scene_image_prims(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)),
                    "crt_scene_image_prims")
         return out
+
+    IMAGE_ARRAYS = ("nodes", "leaves", "packets", "indices", "prims", "instances", "normals")
+
+    def image_arrays(self):
+        """Host-only: the arrays of the device image as uint8 buffers by name (IMAGE_ARRAYS) and the view's plain fields
+        (crt_scene_image.h, crt_scene_image_array): root, has_packets, n_nodes, n_packets, direct_leaves, pool_stack, cold. Needs no GPU."""
+        import numpy as np
+        out, view = {}, (C.c_uint32 * 8)()
+        for which, name in enumerate(self.IMAGE_ARRAYS):
+            n = C.c_size_t()
+            _check(lib().crt_scene_image_array(self.h, which, None, 0, C.byref(n), view), "crt_scene_image_array")
+            buf = np.zeros(max(n.value, 16), np.uint8)  # never a NULL base, even for an empty array
+            if n.value:
+                _check(lib().crt_scene_image_array(self.h, which, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n), view),
+                       "crt_scene_image_array")
+            out[name] = buf
+        fields = dict(zip(("root", "has_packets", "n_nodes", "n_packets", "direct_leaves", "pool_stack", "cold"), map(int, view)))
+        return out, fields
 
     def root_touched(self, rays, t_min=0.001, t_max=float("inf")):
         """Host-only: the renderer's root cull as a function (crt.h, crt_scene_root_touched_n). rays: [n, >= 6] float32
@@ -895,15 +917,16 @@ class Renderer:
         return {n: (int(w[k]), (l[k] / (64.0 * w[k])) if w[k] else 0.0) for k, n in enumerate(self.SHADE_CLASSES)}
 
     def pipeline(self):
-        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'slim_state', 'volumes', 'grid'}: the launch pipeline chosen for this scene
+        """{'fused', 'wide', 'shade_pipe', 'root_cull', 'slim_state', 'volumes', 'camera_trace', 'grid'}: the launch pipeline chosen for this scene
         (crt.h, crt_renderer_pipeline); shade_pipe: the last batch's shade launches were the pipelined four-wave instance;
         root_cull: its generate launches finished the camera rays that miss every child of the root; slim_state: the
         pipelined launches handed each other the slim path state (a material table in which nothing emits); volumes: the
-        batch was a volume render (set_volumes: the volume stage ran between extend and shade)."""
+        batch was a volume render (set_volumes: the volume stage ran between extend and shade); camera_trace: k_camera generated
+        and traced the camera rays, and the first extend ran over the rays it deferred."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
         return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
-                    slim_state=bool(out[1] & 8), volumes=bool(out[1] & 16), grid=int(out[2]))
+                    slim_state=bool(out[1] & 8), volumes=bool(out[1] & 16), camera_trace=bool(out[1] & 32), grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""

@@ -340,6 +340,18 @@ int crt_scene_image_prims(CrtScene *s, uint32_t *words16, size_t cap_prims, size
     return (int)CRT_OK;
   });
 }
+int crt_scene_image_array(CrtScene *s, uint32_t which, void *dst, size_t cap_bytes, size_t *n_bytes, uint32_t view[8]) {
+  if (!s || !n_bytes || !view || (cap_bytes && !dst)) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_scene_image_array", [&] {
+    std::vector<unsigned char> bytes;
+    const int rc = scene_image_array(*s->p, which, bytes, view);
+    if (rc != CRT_OK) return rc;
+    *n_bytes = bytes.size();
+    const size_t n = bytes.size() < cap_bytes ? bytes.size() : cap_bytes;
+    if (n) std::memcpy(dst, bytes.data(), n);
+    return (int)CRT_OK;
+  });
+}
 int crt_scene_root_touched_n(CrtScene *s, const float *rays6, size_t n, float t_min, float t_max, uint8_t *touched, uint32_t *root) {
   if (!s || !root || (n && (!rays6 || !touched))) return CRT_ERR_BAD_ARG;
   return abi_guard("crt_scene_root_touched_n", [&] { return scene_root_touched(*s->p, rays6, n, t_min, t_max, touched, root); });

@@ -15,6 +15,7 @@
 
 #include "../../include/crt.h"
 #include "../../include/crt_render_volumes.h"
+#include "../../include/crt_scene_image.h"
 
 namespace crt {
 
@@ -379,7 +380,7 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
 // tests/test_launch_plan.py sweeps the function on the CPU.
 // ---------------------------------------------------------------------------------------------
 enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC,
-                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME };
+                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME, KF_EXTEND_DEFERRED };
 struct InstanceKey {  // a kernel template and its arguments, in the template's order (bools as 0 / 1)
   uint8_t family = KF_NONE;
   uint8_t arg[5] = {0, 0, 0, 0, 0};
@@ -410,6 +411,11 @@ struct InstanceKey {  // a kernel template and its arguments, in the template's 
   CRT_WIDE_DIRECT_INSTANCES_EXTEND(X) \
   X(EXTEND, k_extend, true, 0, 7) X(EXTEND, k_extend, true, 1, 7) \
   X(EXTEND, k_extend, false, 0, 23) X(EXTEND, k_extend, true, 0, 23) X(EXTEND, k_extend, false, 0, 55) X(EXTEND, k_extend, true, 0, 55)
+// k_extend_deferred<STATS, WIDE, COLD>: the first-bounce traversal behind k_camera (LaunchPlan::camera_trace) — the pool
+// engine over the per-segment list of the camera rays k_camera deferred. A list of its own: a plan names the instance
+// through extend_deferred_key(), never in `extend`.
+#define CRT_INSTANCES_EXTEND_DEFERRED(X) /* k_extend_deferred<STATS, WIDE, COLD> */ \
+  X(EXTEND_DEFERRED, k_extend_deferred, false, 1, 0)
 #define CRT_INSTANCES_PATH(X) /* k_path<MATS, LIT, COLD, DRV>: simple-material tables (derived records or raw), then general ones */ \
   X(PATH, k_path, 0, false, 0, true) X(PATH, k_path, 0, false, 7, true) X(PATH, k_path, 0, true, 0, true) X(PATH, k_path, 0, true, 7, true) \
   X(PATH, k_path, 0, false, 0, false) X(PATH, k_path, 0, false, 7, false) X(PATH, k_path, 0, true, 0, false) X(PATH, k_path, 0, true, 7, false) \
@@ -477,14 +483,25 @@ struct PlanInputs {
   // k_volume between extend and shade, the VOL shade instances and — where the shadow stage runs — k_shadow_volume ahead
   // of k_shadow. false: exactly the plan of a renderer that never heard of volumes.
   bool volumes = false;
+  // CRT_CAMERA_TRACE: 0 = generate and the first extend as before, 1 = k_camera wherever the result allows, 2 / 3 = the
+  // same with every surviving ray deferred / with a one-entry stack (tests: the list and the deferred instance), -1 = the
+  // host rule below
+  int camera_trace_knob = -1;
   // per batch
   size_t total = 0;               // paths of the batch
   bool stats = false;             // the stats build (crt_render_samples_stats)
+  bool partial_active = false;    // adaptive stopping with an active list shorter than the frame (Params::active)
   // the build's switches that gate forms (kernels/pathtrace.hip)
   bool cam_compact_build = true, wide_direct_build = CRT_WIDE_DIRECT_BUILD != 0, nopk_build = CRT_NOPK_BUILD != 0;
   bool shade_pipe_build = true, root_cull_build = true;
   int pipe_mat_max = 0;
+  bool camera_trace_build = true;
 };
+// k_camera traces every camera ray in the lane that made it against a window of the tree's top in LDS and a stack of
+// kCamStack entries; a ray that needs more is traced a second time by the pool engine. That pays on the small flat trees
+// whose camera rays rarely leave the window (cornellbox: profiles/README.md). Larger trees run the parent's launches
+// unless CRT_CAMERA_TRACE=1 asks.
+constexpr uint32_t kCameraTraceMaxNodes = 1024;
 // The root cull pays where at least an eighth of the frame shows background: between the share that lost and the shares
 // that won (profiles/README.md — cornellbox, 0.44 of its camera rays culled, +1.7 %; openpbr_showcase, 0.23, +1 %;
 // veach_mis, 0.06, and the two scenes that fill their frame lose 1-3 %).
@@ -530,6 +547,17 @@ struct LaunchPlan {
   // of k_shadow where the shadow stage runs; `shade` then names a KF_SHADE_VOL instance. none = not launched.
   bool volumes = false;
   InstanceKey volume_key, shadow_volume_key;
+  // Camera rays traced where they are made (kernels/pathtrace.hip, k_camera): one launch generates, culls and traces the
+  // batch's camera rays, one ray per lane, and writes their hit records; the first extend is the k_extend_deferred
+  // instance over the few rays k_camera could not finish. `extend` names the same instance whatever this says.
+  // camera_mode: k_camera's test argument — bit 0 every surviving ray defers, bits 8.. a stack limit below kCamStack.
+  bool camera_trace = false;
+  uint32_t camera_mode = 0;
+  InstanceKey extend_deferred_key() const {
+    InstanceKey k = camera_trace ? extend : InstanceKey{};
+    if (camera_trace) k.family = KF_EXTEND_DEFERRED;
+    return k;
+  }
   bool slim_state = false;
   InstanceKey shade_slim_key() const {
     InstanceKey k = slim_state ? shade_early : InstanceKey{};
@@ -621,12 +649,21 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
       if (e.curve) { pl.shadow_key = key(e.cubic ? KF_SHADOW_CUBIC : KF_SHADOW_CURVE, q.stats); shadow_cold = curve_cold; }
       else pl.shadow_key = key(KF_SHADOW, q.stats, width);
     }
+    // k_camera: the per-stage pipeline with camera paths in the compact form (so: unlit, pinhole, static, no volumes), on
+    // the flat four-wave engine without cold state — the one instance k_extend_deferred is built for — of an image with
+    // packets whose root is a node, a depth limit of at least one bounce, every pixel sampling. Not the stats build: its
+    // kernels count the steps of every ray. With or without the root cull.
+    pl.camera_trace = q.camera_trace_build && q.camera_trace_knob != 0 && !q.stats && !q.volumes && !q.partial_active &&
+                      pl.cam_compact != 0 && width == 1 && pl.ext_cold == 0 && q.max_depth >= 1 && q.scene.root != CRT_INVALID_ID &&
+                      q.scene.n_packets > 0 && q.scene.has_packets != 0 && q.scene.direct_leaves == 0 &&
+                      (q.camera_trace_knob > 0 || q.scene.n_nodes <= kCameraTraceMaxNodes);
+    if (pl.camera_trace) pl.camera_mode = q.camera_trace_knob == 2 ? 1u : (q.camera_trace_knob == 3 ? (1u << 8) : 0u);
   }
   const bool ok = !(q.volumes && q.stats) &&  // the stats build counts no walk: refused (crt_render_samples_stats)
                   (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
                   (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; }
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.camera_trace = false; pl.camera_mode = 0; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }
@@ -654,6 +691,7 @@ struct Knobs {
   int mat_dedup = 1, partition = -1, simple = 1, prefer_stage = -1, cam_compact = 1, root_cull = -1, shade_wide = -1, shade_pipe = 1, fused = -1;
   int mat_derived = 1;        // CRT_MAT_DERIVED: 0 = the shade kernels compute the per-material constants at every vertex again
   int slim_state = 1;         // CRT_SLIM_STATE: 0 = the pipelined shade kernel hands itself the full path state
+  int camera_trace = -1;      // CRT_CAMERA_TRACE: 0 never k_camera, 1 wherever allowed, 2 / 3 the test forms (PlanInputs), unset: the host rule
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
 };
@@ -686,6 +724,9 @@ struct Scene : std::enable_shared_from_this<Scene> {
 int scene_image_check(const Scene &scene, uint64_t out[8]);
 // Host-only: the image's primitive records (scene.cpp).
 int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out);
+// Host-only: array `which` of the image (nodes, leaves, packets, indices, prims, instances, normals) as bytes, and the
+// view's plain fields: root, has_packets, n_nodes, n_packets, direct_leaves, pool_stack, cold, 0 (scene.cpp).
+int scene_image_array(const Scene &scene, uint32_t which, std::vector<unsigned char> &out, uint32_t view[8]);
 // Host-only: node_touched on the root node of the image this scene would upload, for n rays of six floats (origin,
 // direction): out[i] = 1 when ray i touches a child of the root. *root = the image's root (CRT_INVALID_ID: an empty
 // scene, every out[i] = 0).

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "shade.hip.h"
+#include "traverse_camera.hip.h"
 #include "traverse_pool.hip.h"
 #include "volume.hip.h"
 
@@ -159,6 +160,9 @@ struct Counters {
   // crt_renderer_shade_class_stats: per material class, the wave executions of the vertex step that contained a
   // vertex of the class, and how many of their 64 lanes held one (lanes / (64 * waves) = the class's lane utilisation)
   unsigned long long cls_waves[4], cls_lanes[4];
+  // k_camera: the camera rays of the segment it left to the first extend (k_extend_deferred); their slot numbers are in
+  // the segment's part of the OTHER state buffer's plane `a`, which is free until the first shade writes its survivors
+  uint32_t cam_defer[kMaxGrid];
 };
 
 __device__ __forceinline__ uint32_t dir_bin(float dx, float dy, float dz) {
@@ -598,15 +602,127 @@ __global__ __launch_bounds__(kBlock) void k_generate(Params P, PathSoA S, Counte
   else generate_segment(P, S, C, sample_begin, n_samples, sobol_tab, false);
 }
 
+// ---- camera: generate, root cull and the camera rays' closest-hit traversal in ONE kernel (LaunchPlan::camera_trace) ----
+// The 64 camera rays of a wave are 64 neighbouring pixels: they walk the tree together, so the pool engine's scheduler has
+// nothing to repair on them, and a camera ray is in registers here. The sample loop is generate_segment_cull's — the same
+// dealing, camera_sample, node_touched and escaped_to_sky; without the cull (Params::root_cull == 0) every sample goes on
+// and keeps its slot, as in generate_segment — and a surviving ray is then traced in the lane that made it
+// (traverse_camera.hip.h: the pool engine's node and packet steps, one ray per lane, the top of the tree and its packets
+// read from LDS, a kCamStack-entry stack per lane in LDS) and its hit record written as extend_segment's emit writes it.
+// Planes `a` and `d` go out for the first shade as before. What the loop does not handle — scalar leaf entries, a deeper
+// stack — it leaves to the first extend: the ray's slot number goes to the segment's list in the other state buffer's
+// plane `a`, the count to Counters::cam_defer, its hit record stays unwritten, and k_extend_deferred traces it from the
+// root. Only the compact camera forms occur (plan_launches). mode: bit 0 every surviving ray is deferred, bits 8.. a
+// stack limit below kCamStack (tests of the list and of the deferred instance).
+constexpr int kCamLdsDwords = kCamWindow * kLdsNodeStride + kCamStack * kBlock;
+static_assert((kSobolLdsWords + kCamLdsDwords) * 4 + 512 <= 40 * 1024, "four workgroups of k_camera per CU");
+__global__ __launch_bounds__(kBlock, 4) void k_camera(Params P, PathSoA S, uint32_t *defer_plane, HitSoA H, Counters *C,
+                                                      uint32_t sample_begin, uint32_t n_samples, float4 *staging, uint32_t mode) {
+  __shared__ uint32_t sobol_tab[kSobolLdsWords];
+  __shared__ __attribute__((aligned(16))) uint32_t cam_lds[kCamLdsDwords];
+  __shared__ uint32_t cam_ctr[3];  // survivors appended (live slots) | camera rays finished here | rays left to the first extend
+  const bool cull = P.root_cull != 0;  // uniform
+  float bmin[3][4], bmax[3][4];
+  uint32_t child[4];
+  {
+    const WideNode &root = P.scene.nodes[P.scene.root];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int l = 0; l < 4; l++) { bmin[a][l] = root.bmin[a][l]; bmax[a][l] = root.bmax[a][l]; }
+#pragma unroll
+    for (int l = 0; l < 4; l++) child[l] = root.child[l];
+  }
+  if (threadIdx.x < 3) cam_ctr[threadIdx.x] = 0;
+  uint32_t *lds_nodes = cam_lds;
+  uint32_t *stk = cam_lds + kCamWindow * kLdsNodeStride + threadIdx.x;  // entry e of this lane: stk[e * kBlock]
+  uint32_t n_lds_pk;
+  const uint32_t n_lds = stage_nodes(P.scene, lds_nodes, kCamWindow, n_lds_pk);  // ends with a workgroup barrier
+  sobol_tables_init(sobol_tab);                                                  // ... as does this
+  const bool defer_all = (mode & 1u) != 0;
+  const uint32_t want_stack = mode >> 8;
+  const uint32_t pstack = (want_stack == 0 || want_stack > (uint32_t)kCamStack) ? (uint32_t)kCamStack : want_stack;
+  const size_t total = (size_t)P.n_act * n_samples;
+  const size_t seg0 = (size_t)blockIdx.x * kBins * P.seg_cap;
+  uint32_t *list = defer_plane + 4 * seg0;  // 4 * seg_cap words of the segment's plane; at most seg_cap are used
+  const V3 cam_o = ld3(P.camera.origin) + splat(0.0f);  // the pinhole camera's origin, as the compact form's readers take it
+  uint32_t n_culled = 0, n_valid = 0;
+  for (size_t k0 = 0; k0 < P.seg_cap; k0 += kBlock) {  // uniform: seg_cap is a multiple of the workgroup's width
+    if (camera_slot_sample(k0) >= total) break;        // uniform
+    const size_t g = camera_slot_sample(k0 + threadIdx.x);
+    CameraSample cs;
+    cs.o = splat(0.0f); cs.d = splat(0.0f); cs.time = 0.0f; cs.pattern = 0; cs.pix = 0; cs.sl = 0;
+    bool keep = false;
+    if (g < total) {
+      cs = camera_sample(P, g, sample_begin, sobol_tab);
+      keep = true;
+      n_valid = (uint32_t)(k0 + threadIdx.x) + 1;
+      if (cull) {  // uniform
+        keep = node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);
+        if (!keep) {  // tracer.rs:1321-1342 with L = 0, beta = 1: the first shade's miss step
+          const V3 L = escaped_to_sky(cs.d, splat(1.0f), splat(0.0f));
+          st_nt(&staging[cs.sl * P.n_act + cs.pix], make_float4(L.x, L.y, L.z, 0.0f));
+          n_culled++;
+        }
+      }
+    }
+    // under the cull the survivors are compacted; without it a sample keeps the slot it was dealt
+    uint32_t at = (uint32_t)(k0 + threadIdx.x);
+    if (cull) at = seg_append(keep, &cam_ctr[0]);  // uniform
+    const size_t i = seg0 + at;
+    int res = CAM_MISS;
+    if (keep) {
+      st_nt(&S.a[i], make_float4(cs.d.x, cs.d.y, cs.d.z, __uint_as_float(cs.pattern)));
+      if (P.cam_compact == 2) st_nt(&S.d[i], make_uint4(cs.pattern, cs.pix, (P.max_depth & 0xffffu) << 16, cs.sl));  // uniform
+      float t = 0.0f;
+      uint32_t prim = kInvalid;
+      res = defer_all ? (int)CAM_DEFER
+                      : camera_trace(P.scene, lds_nodes, n_lds, n_lds_pk, stk, kBlock, pstack, 0.001f, CRT_INF, CRT_MASK_CAMERA,
+                                     cam_o.x, cam_o.y, cam_o.z, cs.d.x, cs.d.y, cs.d.z, t, prim);
+      if (res == CAM_HIT) {
+        float4 h;
+        uint32_t gw;
+        camera_hit_record(P.scene, prim, t, cs.d.x, cs.d.y, cs.d.z, h, gw);
+        st_hit(&H.h[i], h);
+        st_hit(&H.geom[i], gw);
+      } else if (res == CAM_MISS) {
+        st_hit(&H.geom[i], kInvalid);
+      }
+    }
+    const bool later = keep && res == CAM_DEFER;
+    const uint32_t li = seg_append(later, &cam_ctr[2]);
+    if (later) list[li] = (uint32_t)i;
+  }
+  add_stat(&cam_ctr[1], n_culled);
+  if (!cull && n_valid) atomicMax(&cam_ctr[0], n_valid);  // live slots = 1 + the largest valid k (valid k form a prefix)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int b = 0; b < kBins; b++) {
+      C->seg[0][blockIdx.x * kBins + b] = b == 0 ? cam_ctr[0] : 0;
+      C->seg[1][blockIdx.x * kBins + b] = 0;
+    }
+    C->shadow[blockIdx.x] = 0;
+    C->cam_defer[blockIdx.x] = cam_ctr[2];
+    if (blockIdx.x == 0) atomicAdd(&C->stats[0], (unsigned long long)total);  // camera_rays (tracer.rs:585)
+    if (cam_ctr[1]) {  // closest_hit and escaped, at the indices shade's miss step feeds
+      atomicAdd(&C->stats[1], (unsigned long long)cam_ctr[1]);
+      atomicAdd(&C->stats[6], (unsigned long long)cam_ctr[1]);
+    }
+  }
+}
+
 // ---- extend: World::intersect (rt_world.rs:207-232) for every live path ----
 // COMPACT: the 16-byte camera path form may occur (per-stage launches only: the fused kernel never sets it, and its
 // fetch has no registers for the branch — 13 -> 27, 33 -> 97, 52 -> 122 spilled registers in the lit k_path instances).
-template <bool STATS, int WIDE, int COLD, bool COMPACT>
+// DEFER (k_extend_deferred): the rays are the camera rays k_camera left to this launch — their slot numbers come from the
+// segment's list (defer_list: the other state buffer's plane `a`), their count from Counters::cam_defer.
+template <bool STATS, int WIDE, int COLD, bool COMPACT, bool DEFER = false>
 __device__ __forceinline__ void extend_segment(const Params &P, const PathSoA &S, const HitSoA &H, Counters *C, int cur,
-                                               int first, CrtTravStats *tstats, uint32_t *engine_lds) {
+                                               int first, CrtTravStats *tstats, uint32_t *engine_lds,
+                                               const uint32_t *defer_list = nullptr) {
   __shared__ uint32_t pre[kBins + 1];
   bins_prefix(&C->seg[cur][blockIdx.x * kBins], pre);
-  const uint32_t n = pre[kBins];
+  const uint32_t n = DEFER ? C->cam_defer[blockIdx.x] : pre[kBins];
   if (n == 0) return;  // uniform per workgroup
   __shared__ uint32_t next;
   if (threadIdx.x == 0) next = 0;
@@ -617,7 +733,7 @@ __device__ __forceinline__ void extend_segment(const Params &P, const PathSoA &S
   auto fetch = [&](bool want, RayIn &in) -> bool {
     uint32_t k;
     if (!lds_take(want, &next, n, k)) return false;
-    const uint32_t i = bin_slot(k, pre, P.seg_cap);
+    const uint32_t i = DEFER ? defer_list[4 * (size_t)blockIdx.x * kBins * P.seg_cap + k] : bin_slot(k, pre, P.seg_cap);
     if (CRT_CAM_COMPACT_BUILD && COMPACT && first && P.cam_compact) {  // uniform: camera paths as 16-byte records (generate_segment)
       const float4 A = ld_nt(&S.a[i]);
       const V3 o = ld3(P.camera.origin) + splat(0.0f);
@@ -655,6 +771,14 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend(
                                                                      int first, CrtTravStats *tstats) {
   __shared__ __attribute__((aligned(16))) uint32_t engine_lds[WIDE ? kEngineLdsWide : kEngineLdsDwords];
   extend_segment<STATS, WIDE, COLD, true>(P, S, H, C, cur, first, tstats, engine_lds);
+}
+// The first extend behind k_camera: the same engine instance over the segment's list of deferred camera rays (usually a
+// few per cent of the segment, often none). A kernel of its own, so that k_extend — every later bounce — is untouched.
+template <bool STATS, int WIDE, int COLD>
+__global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend_deferred(Params P, PathSoA S, HitSoA H, Counters *C, int cur,
+                                                                              int first, CrtTravStats *tstats, const uint32_t *defer_list) {
+  __shared__ __attribute__((aligned(16))) uint32_t engine_lds[WIDE ? kEngineLdsWide : kEngineLdsDwords];
+  extend_segment<STATS, WIDE, COLD, true, true>(P, S, H, C, cur, first, tstats, engine_lds, defer_list);
 }
 
 // ---- shade: one iteration of trace_path's loop body for every live path (tracer.rs:1118-1530) ----
@@ -1875,6 +1999,7 @@ __global__ __launch_bounds__(kBlock) void k_film_out(const float4 *film, uint32_
 // (plan_launches); a key without a row is an error, never another instance.
 // ---------------------------------------------------------------------------------------------
 using ExtendFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, CrtTravStats *);
+using ExtendDeferredFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, CrtTravStats *, const uint32_t *);
 using PathFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, float4 *, uint32_t, uint32_t, uint32_t, int);
 using ShadeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int);
 using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int, uint32_t, int);
@@ -1884,6 +2009,7 @@ template <class Fn>
 struct InstanceRow { InstanceKey key; Fn fn; };
 #define CRT_ROW(family, kernel, ...) {CRT_INSTANCE_KEY(family, kernel, __VA_ARGS__), kernel<__VA_ARGS__>},
 static const InstanceRow<ExtendFn> kExtendRows[] = {CRT_INSTANCES_EXTEND(CRT_ROW)};
+static const InstanceRow<ExtendDeferredFn> kExtendDeferredRows[] = {CRT_INSTANCES_EXTEND_DEFERRED(CRT_ROW)};
 static const InstanceRow<PathFn> kPathRows[] = {CRT_INSTANCES_PATH(CRT_ROW)};
 static const InstanceRow<ShadeFn> kShadeRows[] = {CRT_INSTANCES_SHADE(CRT_ROW)};
 static const InstanceRow<ShadePipeFn> kShadePipeRows[] = {CRT_INSTANCES_SHADE_PIPE(CRT_ROW) CRT_INSTANCES_SHADE_PIPE_SLIM(CRT_ROW)};
@@ -2182,6 +2308,7 @@ struct Renderer {
     in.mat_index = P.mat_index != nullptr; in.partition = P.partition; in.n_materials = P.n_materials; in.max_depth = P.max_depth;
     in.class_stats = P.class_stats;
     in.volumes = volumes != nullptr;
+    in.partial_active = p.active != nullptr;
     if (in.volumes && stats) {
       set_error_text("render refused: the stats build does not run volume renders");
       return CRT_ERR_UNSUPPORTED;
@@ -2219,6 +2346,7 @@ struct Renderer {
     const LaunchPlan plan = last_plan;
     PathFn path;
     ExtendFn extend;
+    ExtendDeferredFn extend_deferred;
     ShadeFn shade;
     ShadePipeFn shade_pipe, shade_slim;
     ShadowFn shadow;
@@ -2228,8 +2356,10 @@ struct Renderer {
     if (!find_instance(kPathRows, plan.path, path) || !find_instance(kExtendRows, plan.extend, extend) ||
         (!plan.volumes && !find_instance(kShadeRows, plan.shade, shade)) || !find_instance(kShadePipeRows, plan.shade_early, shade_pipe) ||
         !find_instance(kShadePipeRows, plan.shade_slim_key(), shade_slim) ||
-        !find_instance(kShadowRows, plan.shadow_key, shadow))
+        !find_instance(kShadowRows, plan.shadow_key, shadow) ||
+        !find_instance(kExtendDeferredRows, plan.extend_deferred_key(), extend_deferred))
       return CRT_ERR_UNSUPPORTED;
+    if (plan.camera_trace && (!extend_deferred || plan.cam_compact == 0 || plan.fused)) return CRT_ERR_UNSUPPORTED;
     float4 *staging = B.staging;
     // the film fold: plain sum, or with the luminance statistics and the stopping rule, then the new active list
     auto fold = [&]() -> int {
@@ -2254,7 +2384,12 @@ struct Renderer {
       timed(0, st, [&] { hipLaunchKernelGGL(path, dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], H, Q, C, staging, sample_begin, n_samples, 0u, 0); });
       return fold();
     }
-    timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples, staging); });
+    // generate — or, where the plan says so, k_camera: generate, cull and the camera rays' traversal in one launch, whose
+    // first extend below only picks up the rays it deferred
+    if (plan.camera_trace)
+      timed(3, st, [&] { hipLaunchKernelGGL(k_camera, dim3(grid), dim3(kBlock), 0, st, p, S[0], reinterpret_cast<uint32_t *>(S[1].a), H, C, sample_begin, n_samples, staging, plan.camera_mode); });
+    else
+      timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples, staging); });
     int cur = 0;
     for (uint32_t it = 0; it <= P.max_depth; it++) {
       if (it >= plan.tail_at) {  // the tail: what is left of the batch in one launch of the path-loop kernel
@@ -2262,7 +2397,10 @@ struct Renderer {
         break;
       }
       const int first = it == 0 ? 1 : 0;
-      timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
+      if (first && plan.camera_trace)
+        timed(0, st, [&] { hipLaunchKernelGGL(extend_deferred, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats, reinterpret_cast<const uint32_t *>(S[1 - cur].a)); });
+      else
+        timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
       if (plan.volumes) {  // the walk, then the VOL shade instance (plane c is k_volume's to write: never `first`), then the shadow segments' walk
         timed(3, st, [&] { hipLaunchKernelGGL(k_volume, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, vol); });
         timed(1, st, [&] { hipLaunchKernelGGL(shade_vol, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (int)it >= plan.noclassify_from ? 2 : 0, B.qseed); });
@@ -2496,6 +2634,8 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   in.noclassify_from = knobs.noclassify_from;
   in.shade_pipe = knobs.shade_pipe;
   in.slim_state = knobs.slim_state;
+  in.camera_trace_knob = knobs.camera_trace;
+  in.camera_trace_build = kRootCullBuild && CRT_CAM_COMPACT_BUILD != 0;
   in.no_emitter = table_has_no_emitter(materials, n_materials);  // of the table the kernels read (deduplicated or not)
   in.mat_derived = knobs.mat_derived != 0;
   in.tail_from = knobs.tail_from;
@@ -2676,7 +2816,7 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   const LaunchPlan &plan = r->r.last_plan;  // every bit below is a per-stage one: plan_launches sets none of them on a fused plan
   out[0] = plan.fused ? 1u : 0u;
   out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u) |
-           (plan.volumes ? 16u : 0u);
+           (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

@@ -238,6 +238,7 @@ Knobs read_knobs() {
   if (num("CRT_SHADE_PIPE", v)) k.shade_pipe = v != 0;
   if (num("CRT_MAT_DERIVED", v)) k.mat_derived = v != 0;
   if (num("CRT_SLIM_STATE", v)) k.slim_state = v != 0;
+  if (num("CRT_CAMERA_TRACE", v)) k.camera_trace = (v >= 0 && v <= 3) ? (int)v : 1;
   if (num("CRT_FUSED", v)) k.fused = v != 0;
   if (num("CRT_NOCLASSIFY_FROM", v)) k.noclassify_from = (int)std::min<long long>(std::max<long long>(v, 0), 1 << 30);
   if (num("CRT_TAIL_FROM", v)) k.tail_from = (int)std::min<long long>(std::max<long long>(v, 0), 1 << 30);
@@ -751,6 +752,30 @@ int scene_root_touched(const Scene &scene, const float *rays6, size_t n, float t
     const float *r = rays6 + 6 * i;
     out[i] = node_touched(nd.bmin, nd.bmax, nd.child, r[0], r[1], r[2], r[3], r[4], r[5], t_min, t_max) ? 1 : 0;
   }
+  return CRT_OK;
+}
+
+namespace {
+void fill_view_fields(const FlatImage &im, DevScene &v);
+}
+// Host-only: one array of the image Scene::ensure_device would upload, as bytes, and the view's plain fields — what a
+// host build of a traversal header needs to run on the CPU (tests/host_shade/camera_host.cpp).
+int scene_image_array(const Scene &scene, uint32_t which, std::vector<unsigned char> &out, uint32_t view[8]) {
+  FlatImage im;
+  const int rc = flatten_image(scene, im);
+  if (rc != CRT_OK) return rc;
+  const Flat &f = im.f;
+  const void *src[7] = {f.nodes.data(), f.leaves.data(), f.packets.data(), f.indices.data(), f.prims.data(), f.instances.data(), f.normals.data()};
+  const size_t sz[7] = {f.nodes.size() * sizeof(WideNode), f.leaves.size() * sizeof(Leaf), f.packets.size() * sizeof(Tri4),
+                        f.indices.size() * sizeof(uint32_t), f.prims.size() * sizeof(DevPrim), f.instances.size() * sizeof(DevInstance),
+                        f.normals.size() * sizeof(float)};
+  if (which >= 7) { set_error_text("crt_scene_image_array: no array %u (0..6)", which); return CRT_ERR_BAD_ARG; }
+  out.resize(sz[which]);
+  if (sz[which]) std::memcpy(out.data(), src[which], sz[which]);
+  DevScene v{};
+  fill_view_fields(im, v);
+  view[0] = v.root; view[1] = v.has_packets; view[2] = v.n_nodes; view[3] = v.n_packets; view[4] = v.direct_leaves;
+  view[5] = v.pool_stack; view[6] = v.cold; view[7] = 0;
   return CRT_OK;
 }
 

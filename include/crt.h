@@ -458,7 +458,9 @@ int crt_renderer_shade_class_stats(CrtRenderer *r, int enable, uint64_t out_wave
  * four-wave instance (unlit simple-material scenes of one material class whose material table fits its LDS arena beside
  * the staging blocks; CRT_SHADE_PIPE=0: never), | 8 when those launches handed each other the slim 48-byte path state
  * (a material table in which nothing emits; CRT_SLIM_STATE=0: never), | 16 when the batch was a volume render (an
- * aggregate bound with crt_renderer_set_volumes: the volume stage ran between extend and shade of every bounce);
+ * aggregate bound with crt_renderer_set_volumes: the volume stage ran between extend and shade of every bounce), | 32
+ * when one launch generated, culled and traced the batch's camera rays and the first extend only picked up the rays that
+ * launch deferred (unlit pinhole scenes on the flat four-wave engine; CRT_CAMERA_TRACE=0: never);
  * out[2] = workgroups (= queue segments) per launch.
  * The renderer takes the per-stage form for batches of >= 96 Mi paths and the fused kernel for smaller ones and for the
  * tail of a large one. Environment CRT_FUSED / CRT_WIDE / CRT_STAGE_MIN_PATHS / CRT_GRID_MULT override. */
