@@ -185,6 +185,11 @@ ABI_SYMBOLS = [
 ABI_SYMBOLS_RENDER_VOLUMES = ["crt_renderer_set_volumes"]
 # include/crt_scene_image.h: the host-only hand-out of the scene image's arrays, declared beside crt.h for the same reason.
 ABI_SYMBOLS_SCENE_IMAGE = ["crt_scene_image_array"]
+# include/crt_guiding.h: the path guiding field (guiding.py), declared beside crt.h for the same reason.
+ABI_SYMBOLS_GUIDING = [
+    "crt_guiding_config_default", "crt_guiding_new", "crt_guiding_free", "crt_guiding_update", "crt_guiding_image",
+    "crt_guiding_stats", "crt_guiding_sample_n", "crt_guiding_pdf_n", "crt_material_scatter_guided_n",
+]
 
 _lib = None
 
@@ -318,6 +323,19 @@ def lib():
         L.crt_volumes_sample_n.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
     if hasattr(L, "crt_renderer_set_volumes"):  # volume renders (absent from older A/B variant libraries)
         L.crt_renderer_set_volumes.argtypes = [vp, vp]
+    if hasattr(L, "crt_guiding_new"):  # the path guiding field (guiding.py; absent from older A/B variant libraries)
+        L.crt_guiding_config_default.restype = None
+        L.crt_guiding_config_default.argtypes = [vp]
+        L.crt_guiding_new.restype = vp
+        L.crt_guiding_new.argtypes = [fp, fp, vp]
+        L.crt_guiding_free.restype = None
+        L.crt_guiding_free.argtypes = [vp]
+        L.crt_guiding_update.argtypes = [vp, vp, C.c_size_t, C.c_uint32]
+        L.crt_guiding_image.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.crt_guiding_stats.argtypes = [vp, vp]
+        L.crt_guiding_sample_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.crt_guiding_pdf_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.crt_material_scatter_guided_n.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
     _lib = L
     return L
 
@@ -1046,4 +1064,5 @@ from . import exr  # noqa: E402,F401  (EXR writer / reader + the reference's exr
 from . import stats  # noqa: E402,F401  (RenderStats + the reference's report layout)
 from . import shading  # noqa: E402,F401  (Material / Light as batched device functions: the shading seam)
 from . import volumes  # noqa: E402,F401  (volume regions as batched device functions: fog and smoke behind the ABI)
+from . import guiding  # noqa: E402,F401  (the path guiding field as batched device functions: SD-tree sample, pdf, guided bounce)
 from . import synthetic  # noqa: E402,F401  (scenes built in code: the labelled stand-in for BASELINE config 5)

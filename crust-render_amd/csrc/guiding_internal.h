@@ -1,0 +1,14 @@
+// The guiding field's handle between guiding.cpp (the host field, the image, the device copy) and
+// kernels/guiding_seam.hip (the batched device calls). Not part of the ABI.
+#pragma once
+
+#include "../../include/crt_guiding.h"
+#include "kernels/guiding.hip.h"
+
+namespace crt {
+
+// The device copy of a field's image as the view the kernels take: uploaded on first use, replaced — after waiting for
+// the device — when crt_guiding_update has rebuilt the image since. CRT_ERR_NO_DEVICE without a gfx950 device.
+int guiding_device(CrtGuiding *g, dev::GuideView &out);
+
+}  // namespace crt

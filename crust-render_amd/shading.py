@@ -64,6 +64,20 @@ class DeviceMaterials:
     def scatter_importance(self, d_queries, stream=None):  # material.rs:40-45 -> SCATTER_SAMPLE records
         return _launch("crt_material_scatter_n", self.d, self.n, d_queries, 80, 48, stream)
 
+    def scatter_guided(self, field, d_queries, stream=None):
+        """sample_bounce_direction (tracer.rs:777-826) over crt_material_scatter_guided_n: the one-sample mixture of a
+        guiding.GuidingField and scatter_importance. The queries' sampler words are the VERTEX domain; the result's flags
+        gain guiding.FLAG_TRAINED and guiding.FLAG_FROM_GUIDE. -> SCATTER_SAMPLE records"""
+        import torch
+        crt = _crt()
+        n = d_queries.numel() * d_queries.element_size() // 80
+        d_out = torch.empty(max(n * 48, 1), dtype=torch.uint8, device=d_queries.device)
+        rc = crt.lib().crt_material_scatter_guided_n(field.h, C.c_void_p(self.d.data_ptr() if self.n else 0), self.n,
+                                                     C.c_void_p(d_queries.data_ptr()), n, C.c_void_p(d_out.data_ptr()),
+                                                     crt._stream_ptr(stream))
+        crt._check(rc, "crt_material_scatter_guided_n")
+        return d_out[:n * 48]
+
     def eval(self, d_queries, stream=None):  # material.rs:56-74 -> BSDF_EVAL records
         return _launch("crt_material_eval_n", self.d, self.n, d_queries, 80, 32, stream)
 

@@ -574,7 +574,7 @@ def _volume_region(prim, world):
                 name=prim.name, **field)
 
 
-def load(path, width=None, height=None, cubic_curves=False, environment_maps=False, volumes=False):
+def load(path, width=None, height=None, cubic_curves=False, environment_maps=False, volumes=False, path_guiding=False):
     """Reads a .usda file into a SceneDesc. width/height override the RenderSettings resolution BEFORE the
     camera is built (the aspect ratio feeds Camera::new; the reference can only do this by editing the USD).
     cubic_curves: decode cubic BasisCurves prims into cubic spans (Geometry::CubicCurves) as the reference's importer
@@ -582,7 +582,11 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
     environment_maps: decode a DomeLight's inputs:texture:file (a lat-long EXR beside the layer) into an environment the
     dome importance-samples (usd_import.rs:2389-2460); by default the dome keeps its uniform colour, with a warning.
     volumes: a prim carrying crust:volume:type becomes a region of desc.volumes and never geometry (usd_import.rs:190-209,
-    :435-505); by default such a prim is read as before: by its schema, without a warning."""
+    :435-505); by default such a prim is read as before: by its schema, without a warning.
+    path_guiding: read crust:pathGuiding, crust:guidingTrainIterations (default 4, at least 1) and crust:guidingProb
+    (default 0.5, clamped to [0.1, 0.9] as Renderer::with_guiding clamps it) into desc.settings as guiding,
+    guiding_train_iterations, guiding_prob (usd_import.rs:3056-3062, tracer.rs:696-700) — for a host integrator over
+    guiding.GuidingField; the wavefront renderer ignores the keys. By default the description is what it was."""
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:6] == b"\xfd7zXZ\x00":  # an .xz-compressed stage (scenes/stress.usda.xz: 15 MB of generated text, 0.7 MB packed)
@@ -630,6 +634,13 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
             raise NotImplementedError(f"pixel filter {flt!r}: only box and triangle are on the device path")
         if rs.attr("crust:pixelFilterRadius") is not None:
             s["filter_radius"] = max(float(rs.attr("crust:pixelFilterRadius")), 0.01)
+    if path_guiding:
+        guided = rs if (rs is not None and rs.type == "RenderSettings") else None
+        it = guided.attr("crust:guidingTrainIterations") if guided is not None else None
+        prob = guided.attr("crust:guidingProb") if guided is not None else None
+        s["guiding"] = bool(guided.attr("crust:pathGuiding", False)) if guided is not None else False
+        s["guiding_train_iterations"] = max(int(it) if it is not None else 4, 1)
+        s["guiding_prob"] = min(max(float(prob) if prob is not None else 0.5, 0.1), 0.9)
     if width is not None:
         s["width"] = int(width)
     if height is not None:
