@@ -496,6 +496,9 @@ struct PlanInputs {
   bool shade_pipe_build = true, root_cull_build = true;
   int pipe_mat_max = 0;
   bool camera_trace_build = true;
+  // CRT_CAMERA_VERTEX: 0 = k_camera and a first shade over every camera path, 1 / -1 (unset) = k_camera_vertex wherever
+  // the rule below holds
+  int camera_vertex_knob = -1;
 };
 // k_camera traces every camera ray in the lane that made it against a window of the tree's top in LDS and a stack of
 // kCamStack entries; a ray that needs more is traced a second time by the pool engine. That pays on the small flat trees
@@ -564,6 +567,10 @@ struct LaunchPlan {
     if (slim_state) k.arg[1] = 1;
     return k;
   }
+  // The first vertex shaded in the lane that traced the camera ray (kernels/pathtrace.hip, k_camera_vertex): the camera
+  // launch is k_camera_vertex<shade_early's table>, the first extend the ordinary `extend` instance over the rays that
+  // launch deferred, the first shade `shade_early` (or its slim instance) in append mode. Every field above keeps its value.
+  bool camera_vertex = false;
 };
 // The EngineSelect a traversal instance of width w amounts to on this image (0 = three waves, 1 = four, the flat engine
 // copy only, 2 = four, the direct copy only) — run_traversal picks the three-wave kernels' copy from the image.
@@ -658,12 +665,15 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
                       q.scene.n_packets > 0 && q.scene.has_packets != 0 && q.scene.direct_leaves == 0 &&
                       (q.camera_trace_knob > 0 || q.scene.n_nodes <= kCameraTraceMaxNodes);
     if (pl.camera_trace) pl.camera_mode = q.camera_trace_knob == 2 ? 1u : (q.camera_trace_knob == 3 ? (1u << 8) : 0u);
+    // k_camera_vertex: k_camera's batches whose first shade is the pipelined instance (unlit, simple materials, the whole
+    // table in LDS: the vertex function the two kernels share) and has a vertex to shade — a depth limit of at least 1.
+    pl.camera_vertex = pl.camera_trace && pl.shade_piped() && q.max_depth >= 1 && q.camera_vertex_knob != 0;
   }
   const bool ok = !(q.volumes && q.stats) &&  // the stats build counts no walk: refused (crt_render_samples_stats)
                   (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
                   (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.camera_trace = false; pl.camera_mode = 0; }
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }
@@ -692,6 +702,7 @@ struct Knobs {
   int mat_derived = 1;        // CRT_MAT_DERIVED: 0 = the shade kernels compute the per-material constants at every vertex again
   int slim_state = 1;         // CRT_SLIM_STATE: 0 = the pipelined shade kernel hands itself the full path state
   int camera_trace = -1;      // CRT_CAMERA_TRACE: 0 never k_camera, 1 wherever allowed, 2 / 3 the test forms (PlanInputs), unset: the host rule
+  int camera_vertex = -1;     // CRT_CAMERA_VERTEX: 0 never k_camera_vertex, 1 or unset wherever the plan's rule holds
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
 };

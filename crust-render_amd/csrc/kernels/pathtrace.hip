@@ -34,6 +34,7 @@
 #include "shade.hip.h"
 #include "traverse_camera.hip.h"
 #include "traverse_pool.hip.h"
+#include "vertex_simple.hip.h"
 #include "volume.hip.h"
 
 namespace crt {
@@ -54,9 +55,7 @@ namespace {
 #endif
 
 enum { K_CAMERA = 0, K_PATH = 1, K_TIME = 2 };                 // tracer.rs:20-22 (off root)
-enum { K_NEE = 0, K_NEE_SHADOW = 1, K_BSDF = 2, K_PHASE = 4, K_RR = 5, K_MEDIUM = 6, K_VOLUME = 7 };  // tracer.rs:23-30 (off vertex)
-constexpr int kRrStartBounce = 3;                              // tracer.rs:46
-constexpr float kRrMinProb = 0.05f;                            // tracer.rs:47
+// (the domains off a vertex, K_NEE .. K_VOLUME, and the roulette constants: vertex_simple.hip.h)
 constexpr uint32_t kFilmTarget = 0x80000000u;
 constexpr uint32_t kPrevValid = 1u << 16, kPrevDelta = 1u << 17;
 constexpr int kMediumShift = 18;             // aux[18:32): 1-based compact id of the interior medium the ray travels in
@@ -1521,18 +1520,20 @@ __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__bui
 template <bool DRV, bool SLIM>
 __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                                    Counters *C, int cur, float4 *staging, uint32_t *arena /* kArenaWide */,
-                                                   bool first, uint32_t it, bool out_full) {
+                                                   bool first, uint32_t it, bool out_full, bool append) {
   constexpr bool STAMPS = CRT_SHADE_STAMPS != 0;
   __shared__ uint32_t lds_ctr[10];   // [2..8] statistics
   __shared__ uint32_t out_n;         // survivors
   __shared__ uint32_t ring_tail[2];  // entries ever appended: hits, misses
   const uint32_t n = uniform(((const volatile uint32_t *)C->seg[cur])[blockIdx.x]);
+  // append (uniform; behind k_camera_vertex): the other buffer's segment already holds that kernel's survivors, counted in
+  // its seg word — this launch's survivors go behind them
   if (n == 0) {  // nothing lives in this segment: publish empty outputs and leave
-    if (threadIdx.x == 0) { C->seg[1 - cur][blockIdx.x] = 0; C->shadow[blockIdx.x] = 0; }
+    if (threadIdx.x == 0) { if (!append) C->seg[1 - cur][blockIdx.x] = 0; C->shadow[blockIdx.x] = 0; }
     return;
   }
   if (threadIdx.x < 10) lds_ctr[threadIdx.x] = 0;
-  if (threadIdx.x == 0) out_n = 0;
+  if (threadIdx.x == 0) out_n = append ? ((const volatile uint32_t *)C->seg[1 - cur])[blockIdx.x] : 0u;
   if (threadIdx.x < 2) ring_tail[threadIdx.x] = 0;
   sobol_tables_init(arena);  // ends with a workgroup barrier
   // the material table, always in LDS here (kPipeMatMax) and read through an LDS pointer
@@ -1711,56 +1712,14 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
         rec.normal = v3(hh.y, hh.z, hh.w);
         rec.p = ro + rd * rec.t;  // ray.at(t), rt_world.rs:221
         const auto mat = MatTable<DRV>::view(mats, P, mat_i);
-        const float emission_weight = 1.0f;  // bounce_emission_weight without lights (tracer.rs:930-953)
-        if (remaining <= 0) {  // tracer.rs:1123-1149: depth exhausted, last-vertex emission only
-          s_depth++;
-          if (prev_valid) {
-            s_closest++;
-            const float cos_o = fabs_(dot(normalize(rd), rec.normal));
-            const V3 emitted = mat_emitted_directional<true>(mat, cos_o);
-            if (len2(emitted) > 0.0f) L = L + beta * (emitted * emission_weight);
-          }
-        } else {
-          s_closest++;
-          const Sampler vdom = new_domain(Sampler{pattern, P.sample_begin + (aux & 0xffffu)}, (int)n_rec);  // :1121
-          const V3 atten = splat(1.0f);
-          const float cos_o = fabs_(dot(normalize(rd), rec.normal));
-          const V3 emitted = mat_emitted_directional<true>(mat, cos_o);
-          V3 emit_here = splat(0.0f);
-          if (prev_valid) {  // tracer.rs:1372-1381
-            if (len2(emitted) > 0.0f) L = L + beta * ((atten * emitted) * emission_weight);
-          } else {
-            emit_here = emitted;
-          }
-          const V3 ba = beta * atten;
-          L = L + ba * emit_here;
-          // indirect lighting by BSDF sampling (tracer.rs:1459-1523)
-          Scatter sample;
-          if (mat_scatter<true>(mat, rd, rec, new_domain(vdom, K_BSDF), sample, arena)) {
-            const V3 dir = normalize(sample.dir);
-            const float cosine = sample.delta ? 1.0f : fabs_(dot(rec.normal, dir));
-            const V3 factor = (sample.value * cosine) / sample.pdf;
-            beta = beta * (atten * factor);
-            bool survived = true;
-            if (n_rec >= (uint32_t)kRrStartBounce) {
-              s_rr_t++;
-              const float p_survive = rclamp(max_elem(beta), kRrMinProb, 1.0f);
-              if (p_survive < 1.0f) {
-                if (draw_rnd1(new_domain(vdom, K_RR)) >= p_survive) {
-                  survived = false;
-                  s_rr_k++;
-                } else {
-                  beta = beta / p_survive;
-                }
-              }
-            }
-            if (survived) {
-              alive = true;
-              n_o = sample.origin; n_d = sample.dir; n_delta = sample.delta;
-            }
-          }
-          s_vertices++;
-        }
+        // the vertex itself: vertex_simple.hip.h, the one source this kernel shares with k_camera_vertex
+        const VertexOut v = vertex_simple(mat, ro, rd, beta, L, rec, pattern, P.sample_begin + (aux & 0xffffu), n_rec, remaining,
+                                          prev_valid, arena);
+        beta = v.beta; L = v.L;
+        alive = v.alive;
+        n_o = v.origin; n_d = v.dir; n_delta = v.delta;  // zero / false where the path ended
+        s_closest += v.closest; s_vertices += v.vertices; s_rr_t += v.rr_tested; s_rr_k += v.rr_killed; s_esc += v.escaped;
+        s_depth += v.depth_ended;
       }
       // survivors go to the other state buffer, finished paths to the film
       const uint32_t j = seg0 + seg_append(alive, &out_n);
@@ -1798,13 +1757,152 @@ __device__ __forceinline__ void shade_segment_pipe(const Params &P, const PathSo
   if (STAMPS && lane == 0)
     for (int s = 0; s < 7; s++) atomicAdd(s < 4 ? &C->cls_waves[s] : &C->cls_lanes[s - 4], t_acc[s]);
 }
-// it, out_full: read by the SLIM instances only.
+// it, out_full: read by the SLIM instances only. first: bit 0 the camera paths' launch, bit 1 append (shade_segment_pipe).
 template <bool DRV, bool SLIM = false>
 __global__ __launch_bounds__(kBlock, CRT_SHADE_WIDE_WAVES) void k_shade_pipe(Params P, PathSoA S, PathSoA N, HitSoA H, Counters *C,
                                                                               int cur, float4 *staging, int first, uint32_t it,
                                                                               int out_full) {
   __shared__ __attribute__((aligned(16))) uint32_t arena[kArenaWide];
-  shade_segment_pipe<DRV, SLIM>(P, S, N, H, C, cur, staging, arena, first != 0, it, out_full != 0);
+  shade_segment_pipe<DRV, SLIM>(P, S, N, H, C, cur, staging, arena, (first & 1) != 0, it, out_full != 0, (first & 2) != 0);
+}
+
+// ---- camera + first vertex: k_camera with the first shade's vertex step behind the trace (LaunchPlan::camera_vertex) ----
+// At bounce 0 nearly every live path is a hit, and k_camera holds its ray, t and primitive in registers — yet it wrote
+// planes a, d and the hit record (52 bytes per path) for a first k_shade_pipe launch that sorts slots none of which
+// needs sorting and gathers the same 52 bytes back through its staging blocks. Here the lane that traced the ray shades
+// its first vertex (vertex_simple.hip.h, the function k_shade_pipe's vertex step calls) with a camera path's constants as
+// literals — origin = the camera's, throughput 1, radiance 0, no vertex recorded, no previous vertex — so the roulette
+// and previous-vertex arms fold away and the arithmetic left is the first shade's, operation for operation.
+//   CAM_HIT    the vertex; a survivor goes to the OTHER state buffer N, compacted with an LDS counter, in the form the
+//              next launch reads (slim_out: planes a, b and the slim c; otherwise the full four planes), a finished path
+//              to its staging film slot
+//   CAM_MISS   finished here as the cull arm finishes its rays: the miss step's arithmetic and counters
+//   CAM_DEFER  the ray goes to the input buffer S, compacted with a second LDS counter, in the root-cull compact form
+//              (planes a and d, Params::cam_compact == 2 — the caller launches the first extend and shade with that
+//              value whatever the cull says): the ordinary extend instance traces the segment's seg[0] rays, the first
+//              k_shade_pipe launch shades them in append mode behind the survivors counted in seg[1]
+// The eight RayStats totals keep their values: closest_hit and vertices per hit, closest_hit and escaped per miss, as the
+// first shade would have added them. LDS: the material table (at most kPipeMatMax records, as k_shade_pipe stages it)
+// beside k_camera's Sobol tables, node window and stacks — the window keeps its kCamWindow strides.
+static_assert((kSobolLdsWords + kCamLdsDwords + kPipeMatMax * kMatDwords) * 4 + 512 <= 40 * 1024, "four workgroups of k_camera_vertex per CU");
+template <bool DRV>
+__global__ __launch_bounds__(kBlock, 4) void k_camera_vertex(Params P, PathSoA S, PathSoA N, Counters *C, uint32_t sample_begin,
+                                                             uint32_t n_samples, float4 *staging, uint32_t mode, int slim_out) {
+  __shared__ uint32_t sobol_tab[kSobolLdsWords];
+  __shared__ __attribute__((aligned(16))) uint32_t cam_lds[kCamLdsDwords];
+  __shared__ __attribute__((aligned(16))) uint32_t mat_lds[kPipeMatMax * kMatDwords];
+  __shared__ uint32_t cam_ctr[4];  // rays left to the first extend | camera rays that escaped here | survivors | vertices
+  const bool cull = P.root_cull != 0;  // uniform
+  float bmin[3][4], bmax[3][4];
+  uint32_t child[4];
+  {
+    const WideNode &root = P.scene.nodes[P.scene.root];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int l = 0; l < 4; l++) { bmin[a][l] = root.bmin[a][l]; bmax[a][l] = root.bmax[a][l]; }
+#pragma unroll
+    for (int l = 0; l < 4; l++) child[l] = root.child[l];
+  }
+  if (threadIdx.x < 4) cam_ctr[threadIdx.x] = 0;
+  {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(MatTable<DRV>::of(P));
+    // at most kPipeMatMax records (plan_launches, shade_pipe_fits)
+    const uint32_t words = (P.n_materials < (uint32_t)kPipeMatMax ? P.n_materials : (uint32_t)kPipeMatMax) * (uint32_t)kMatDwords;
+    for (uint32_t w = threadIdx.x; w < words; w += kBlock) mat_lds[w] = src[w];
+  }
+  const typename MatTable<DRV>::Rec *mats = reinterpret_cast<const typename MatTable<DRV>::Rec *>(mat_lds);
+  uint32_t *lds_nodes = cam_lds;
+  uint32_t *stk = cam_lds + kCamWindow * kLdsNodeStride + threadIdx.x;  // entry e of this lane: stk[e * kBlock]
+  uint32_t n_lds_pk;
+  const uint32_t n_lds = stage_nodes(P.scene, lds_nodes, kCamWindow, n_lds_pk);  // ends with a workgroup barrier
+  sobol_tables_init(sobol_tab);                                                  // ... as does this
+  const bool defer_all = (mode & 1u) != 0;
+  const uint32_t want_stack = mode >> 8;
+  const uint32_t pstack = (want_stack == 0 || want_stack > (uint32_t)kCamStack) ? (uint32_t)kCamStack : want_stack;
+  const size_t total = (size_t)P.n_act * n_samples;
+  const size_t seg0 = (size_t)blockIdx.x * kBins * P.seg_cap;
+  const V3 cam_o = ld3(P.camera.origin) + splat(0.0f);  // the pinhole camera's origin, as the compact form's readers take it
+  uint32_t n_escaped = 0, n_vertices = 0;
+  for (size_t k0 = 0; k0 < P.seg_cap; k0 += kBlock) {  // uniform: seg_cap is a multiple of the workgroup's width
+    if (camera_slot_sample(k0) >= total) break;        // uniform
+    const size_t g = camera_slot_sample(k0 + threadIdx.x);
+    CameraSample cs;
+    cs.o = splat(0.0f); cs.d = splat(0.0f); cs.time = 0.0f; cs.pattern = 0; cs.pix = 0; cs.sl = 0;
+    int res = CAM_MISS;
+    bool valid = false, alive = false;
+    VertexOut v;
+    v.origin = splat(0.0f); v.dir = splat(0.0f); v.beta = splat(1.0f); v.L = splat(0.0f); v.delta = false;
+    if (g < total) {
+      cs = camera_sample(P, g, sample_begin, sobol_tab);
+      valid = true;
+      bool keep = true;
+      if (cull) keep = node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);  // uniform
+      float t = 0.0f;
+      uint32_t prim = kInvalid;
+      if (keep)
+        res = defer_all ? (int)CAM_DEFER
+                        : camera_trace(P.scene, lds_nodes, n_lds, n_lds_pk, stk, kBlock, pstack, 0.001f, CRT_INF, CRT_MASK_CAMERA,
+                                       cam_o.x, cam_o.y, cam_o.z, cs.d.x, cs.d.y, cs.d.z, t, prim);
+      const uint32_t sl = cs.sl & 0xffffu;
+      if (res == CAM_HIT) {  // the first shade's VERTEX step on a camera path
+        float4 h;
+        uint32_t gw;
+        camera_hit_record(P.scene, prim, t, cs.d.x, cs.d.y, cs.d.z, h, gw);
+        HitRec rec;
+        rec.front_face = ((gw >> 31) & 1u) != 0;
+        rec.t = h.x;
+        rec.normal = v3(h.y, h.z, h.w);
+        rec.p = cam_o + cs.d * rec.t;  // ray.at(t), rt_world.rs:221
+        const auto mat = MatTable<DRV>::view(mats, P, gw & 0x7fffffffu);
+        v = vertex_simple(mat, cam_o, cs.d, splat(1.0f), splat(0.0f), rec, cs.pattern, P.sample_begin + sl, 0u, (int)P.max_depth, false,
+                          sobol_tab);
+        alive = v.alive;
+        n_vertices++;
+        if (!alive) st_nt(&staging[sl * P.n_act + cs.pix], make_float4(v.L.x, v.L.y, v.L.z, 0.0f));
+      } else if (res == CAM_MISS) {  // tracer.rs:1321-1342 with L = 0, beta = 1: the first shade's miss step (the cull arm's too)
+        const V3 L = escaped_to_sky(cs.d, splat(1.0f), splat(0.0f));
+        st_nt(&staging[sl * P.n_act + cs.pix], make_float4(L.x, L.y, L.z, 0.0f));
+        n_escaped++;
+      }
+    }
+    // survivors to the other buffer, deferred rays to this one: every wave appends in every round
+    const size_t j = seg0 + seg_append(alive, &cam_ctr[2]);
+    if (alive) {
+      const uint32_t sl = cs.sl & 0xffffu;
+      st_nt(&N.a[j], make_float4(v.origin.x, v.origin.y, v.origin.z, v.dir.x));
+      st_nt(&N.b[j], make_float4(v.dir.y, v.dir.z, v.beta.x, v.beta.y));
+      if (slim_out) {  // uniform: the next shade launch is the slim instance
+        st_nt(&N.c[j], make_float4(v.beta.z, __uint_as_float(cs.pattern), __uint_as_float(cs.pix | (v.delta ? 0x80000000u : 0u)), __uint_as_float(sl)));
+      } else {
+        st_nt(&N.c[j], make_float4(v.beta.z, v.L.x, v.L.y, v.L.z));
+        st_nt(&N.d[j], make_uint4(cs.pattern, cs.pix, 1u | (((P.max_depth & 0xffffu) - 1u) << 16), sl | kPrevValid | (v.delta ? kPrevDelta : 0u)));
+      }
+    }
+    const bool later = valid && res == CAM_DEFER;
+    const size_t i = seg0 + seg_append(later, &cam_ctr[0]);
+    if (later) {
+      st_nt(&S.a[i], make_float4(cs.d.x, cs.d.y, cs.d.z, __uint_as_float(cs.pattern)));
+      st_nt(&S.d[i], make_uint4(cs.pattern, cs.pix, (P.max_depth & 0xffffu) << 16, cs.sl));
+    }
+  }
+  add_stat(&cam_ctr[1], n_escaped);
+  add_stat(&cam_ctr[3], n_vertices);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int b = 0; b < kBins; b++) {
+      C->seg[0][blockIdx.x * kBins + b] = b == 0 ? cam_ctr[0] : 0;
+      C->seg[1][blockIdx.x * kBins + b] = b == 0 ? cam_ctr[2] : 0;
+    }
+    C->shadow[blockIdx.x] = 0;
+    C->cam_defer[blockIdx.x] = 0;
+    if (blockIdx.x == 0) atomicAdd(&C->stats[0], (unsigned long long)total);  // camera_rays (tracer.rs:585)
+    // what the first shade would have added: closest_hit and vertices per hit; closest_hit and escaped per miss
+    const uint32_t esc = cam_ctr[1], hit = cam_ctr[3];
+    if (esc + hit) atomicAdd(&C->stats[1], (unsigned long long)(esc + hit));
+    if (hit) atomicAdd(&C->stats[3], (unsigned long long)hit);
+    if (esc) atomicAdd(&C->stats[6], (unsigned long long)esc);
+  }
 }
 
 // ---- shadow: World::occluded (rt_world.rs:235-237) for the queue; unoccluded requests pay out ----
@@ -2003,6 +2101,7 @@ using ExtendDeferredFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int,
 using PathFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, float4 *, uint32_t, uint32_t, uint32_t, int);
 using ShadeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int);
 using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int, uint32_t, int);
+using CameraVertexFn = void (*)(Params, PathSoA, PathSoA, Counters *, uint32_t, uint32_t, float4 *, uint32_t, int);
 using ShadowFn = void (*)(Params, PathSoA, ShadowSoA, Counters *, float4 *, CrtTravStats *);
 using ShadeVolFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, uint32_t *);
 template <class Fn>
@@ -2386,7 +2485,17 @@ struct Renderer {
     }
     // generate — or, where the plan says so, k_camera: generate, cull and the camera rays' traversal in one launch, whose
     // first extend below only picks up the rays it deferred
-    if (plan.camera_trace)
+    // — or k_camera_vertex: the same with the first vertex shaded behind the trace; its survivors are in S[1] already, and
+    // the first extend and the first shade (append mode, bit 1 of `first`) see only the rays it deferred, which lie in S[0]
+    // in the compact form with plane d whatever the cull says
+    Params p0 = p;  // the launches of bounce 0 behind k_camera_vertex
+    if (plan.camera_vertex) {
+      p0.cam_compact = 2;
+      const uint32_t nx = 1;
+      const int slim_out = (shade_slim && nx <= P.max_depth && nx < plan.tail_at && (int)nx < plan.noclassify_from) ? 1 : 0;
+      const CameraVertexFn fn = plan.shade_early.arg[0] ? k_camera_vertex<true> : k_camera_vertex<false>;
+      timed(3, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], C, sample_begin, n_samples, staging, plan.camera_mode, slim_out); });
+    } else if (plan.camera_trace)
       timed(3, st, [&] { hipLaunchKernelGGL(k_camera, dim3(grid), dim3(kBlock), 0, st, p, S[0], reinterpret_cast<uint32_t *>(S[1].a), H, C, sample_begin, n_samples, staging, plan.camera_mode); });
     else
       timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples, staging); });
@@ -2397,7 +2506,9 @@ struct Renderer {
         break;
       }
       const int first = it == 0 ? 1 : 0;
-      if (first && plan.camera_trace)
+      if (first && plan.camera_vertex)
+        timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p0, S[cur], H, C, cur, first, d_tstats); });
+      else if (first && plan.camera_trace)
         timed(0, st, [&] { hipLaunchKernelGGL(extend_deferred, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats, reinterpret_cast<const uint32_t *>(S[1 - cur].a)); });
       else
         timed(0, st, [&] { hipLaunchKernelGGL(extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
@@ -2412,7 +2523,10 @@ struct Renderer {
         const uint32_t nx = it + 1;
         const int out_full = (nx <= P.max_depth && nx < plan.tail_at && (int)nx < plan.noclassify_from) ? 0 : 1;
         const ShadePipeFn fn = shade_slim ? shade_slim : shade_pipe;
-        timed(1, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, first, it, out_full); });
+        if (first && plan.camera_vertex)
+          timed(1, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p0, S[cur], S[1 - cur], H, C, cur, staging, first | 2, it, out_full); });
+        else
+          timed(1, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, C, cur, staging, first, it, out_full); });
       } else
         timed(1, st, [&] { hipLaunchKernelGGL(shade, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, first | ((int)it >= plan.noclassify_from ? 2 : 0)); });
       if (shadow)
@@ -2635,6 +2749,7 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   in.shade_pipe = knobs.shade_pipe;
   in.slim_state = knobs.slim_state;
   in.camera_trace_knob = knobs.camera_trace;
+  in.camera_vertex_knob = knobs.camera_vertex;
   in.camera_trace_build = kRootCullBuild && CRT_CAM_COMPACT_BUILD != 0;
   in.no_emitter = table_has_no_emitter(materials, n_materials);  // of the table the kernels read (deduplicated or not)
   in.mat_derived = knobs.mat_derived != 0;
@@ -2816,7 +2931,7 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   const LaunchPlan &plan = r->r.last_plan;  // every bit below is a per-stage one: plan_launches sets none of them on a fused plan
   out[0] = plan.fused ? 1u : 0u;
   out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u) |
-           (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u);
+           (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u) | (plan.camera_vertex ? 64u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

@@ -239,6 +239,7 @@ Knobs read_knobs() {
   if (num("CRT_MAT_DERIVED", v)) k.mat_derived = v != 0;
   if (num("CRT_SLIM_STATE", v)) k.slim_state = v != 0;
   if (num("CRT_CAMERA_TRACE", v)) k.camera_trace = (v >= 0 && v <= 3) ? (int)v : 1;
+  if (num("CRT_CAMERA_VERTEX", v)) k.camera_vertex = v != 0 ? 1 : 0;
   if (num("CRT_FUSED", v)) k.fused = v != 0;
   if (num("CRT_NOCLASSIFY_FROM", v)) k.noclassify_from = (int)std::min<long long>(std::max<long long>(v, 0), 1 << 30);
   if (num("CRT_TAIL_FROM", v)) k.tail_from = (int)std::min<long long>(std::max<long long>(v, 0), 1 << 30);

@@ -460,7 +460,9 @@ int crt_renderer_shade_class_stats(CrtRenderer *r, int enable, uint64_t out_wave
  * (a material table in which nothing emits; CRT_SLIM_STATE=0: never), | 16 when the batch was a volume render (an
  * aggregate bound with crt_renderer_set_volumes: the volume stage ran between extend and shade of every bounce), | 32
  * when one launch generated, culled and traced the batch's camera rays and the first extend only picked up the rays that
- * launch deferred (unlit pinhole scenes on the flat four-wave engine; CRT_CAMERA_TRACE=0: never);
+ * launch deferred (unlit pinhole scenes on the flat four-wave engine; CRT_CAMERA_TRACE=0: never), | 64 when that launch
+ * also shaded the first vertex of every camera path it traced, so that the first extend and the first shade launch ran
+ * over the deferred rays alone (with | 2 and | 32, a depth limit of at least 1; CRT_CAMERA_VERTEX=0: never);
  * out[2] = workgroups (= queue segments) per launch.
  * The renderer takes the per-stage form for batches of >= 96 Mi paths and the fused kernel for smaller ones and for the
  * tail of a large one. Environment CRT_FUSED / CRT_WIDE / CRT_STAGE_MIN_PATHS / CRT_GRID_MULT override. */
