@@ -941,12 +941,15 @@ class Renderer:
         pipelined launches handed each other the slim path state (a material table in which nothing emits); volumes: the
         batch was a volume render (set_volumes: the volume stage ran between extend and shade); camera_trace: k_camera generated
         and traced the camera rays, and the first extend ran over the rays it deferred; camera_vertex: k_camera_vertex also
-        shaded their first vertex, and the first extend and shade ran over the rays it deferred."""
+        shaded their first vertex, and the first extend and shade ran over the rays it deferred; pixel_table: that launch
+        read each sample's per-pixel words from the table the renderer filled at creation; cull_root_lds: its root cull
+        read the root node from the launch's LDS window."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
         return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
                     slim_state=bool(out[1] & 8), volumes=bool(out[1] & 16), camera_trace=bool(out[1] & 32),
-                    camera_vertex=bool(out[1] & 64), grid=int(out[2]))
+                    camera_vertex=bool(out[1] & 64), pixel_table=bool(out[1] & 128), cull_root_lds=bool(out[1] & 256),
+                    grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""

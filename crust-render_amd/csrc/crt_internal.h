@@ -499,6 +499,14 @@ struct PlanInputs {
   // CRT_CAMERA_VERTEX: 0 = k_camera and a first shade over every camera path, 1 / -1 (unset) = k_camera_vertex wherever
   // the rule below holds
   int camera_vertex_knob = -1;
+  // CRT_PIXEL_TABLE: 0 = the camera launches compute a sample's per-pixel words every time, 1 / -1 (unset) = they read
+  // the renderer's per-pixel table wherever one was built (pixel_table_ready: creation found a plan that could use it
+  // and the memory for it)
+  int pixel_table_knob = -1;
+  bool pixel_table_ready = false;
+  // CRT_CULL_ROOT_LDS: 1 / -1 (unset) = the camera launch's cull reads the root node from its LDS window every round,
+  // 0 = it holds the root's 28 words in scalar registers, which the kernel parks in VGPR lanes (profiles/README.md)
+  int cull_root_lds_knob = -1;
 };
 // k_camera traces every camera ray in the lane that made it against a window of the tree's top in LDS and a stack of
 // kCamStack entries; a ray that needs more is traced a second time by the pool engine. That pays on the small flat trees
@@ -571,6 +579,12 @@ struct LaunchPlan {
   // launch is k_camera_vertex<shade_early's table>, the first extend the ordinary `extend` instance over the rays that
   // launch deferred, the first shade `shade_early` (or its slim instance) in append mode. Every field above keeps its value.
   bool camera_vertex = false;
+  // The camera launch (k_camera or k_camera_vertex) is the instance whose sample loop reads the per-pixel table and
+  // steps a sample cursor (kernels/camera_pixel.hip.h). Every field above keeps its value.
+  bool pixel_table = false;
+  // The camera launch's cull reads the root from the staged window (k_camera / k_camera_vertex, ROOT_LDS): only where
+  // the root is node 0, the first node stage_nodes copies.
+  bool cull_root_lds = false;
 };
 // The EngineSelect a traversal instance of width w amounts to on this image (0 = three waves, 1 = four, the flat engine
 // copy only, 2 = four, the direct copy only) — run_traversal picks the three-wave kernels' copy from the image.
@@ -668,12 +682,16 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
     // k_camera_vertex: k_camera's batches whose first shade is the pipelined instance (unlit, simple materials, the whole
     // table in LDS: the vertex function the two kernels share) and has a vertex to shade — a depth limit of at least 1.
     pl.camera_vertex = pl.camera_trace && pl.shade_piped() && q.max_depth >= 1 && q.camera_vertex_knob != 0;
+    // the per-pixel table: either camera launch (both run static pinhole batches over every owned pixel), where the
+    // renderer holds one
+    pl.pixel_table = pl.camera_trace && q.pixel_table_knob != 0 && q.pixel_table_ready;
+    pl.cull_root_lds = pl.camera_trace && pl.root_cull && q.cull_root_lds_knob != 0 && q.scene.root == 0 && q.scene.n_nodes > 0;
   }
   const bool ok = !(q.volumes && q.stats) &&  // the stats build counts no walk: refused (crt_render_samples_stats)
                   (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
                   (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; }
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; pl.pixel_table = false; pl.cull_root_lds = false; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }
@@ -703,6 +721,8 @@ struct Knobs {
   int slim_state = 1;         // CRT_SLIM_STATE: 0 = the pipelined shade kernel hands itself the full path state
   int camera_trace = -1;      // CRT_CAMERA_TRACE: 0 never k_camera, 1 wherever allowed, 2 / 3 the test forms (PlanInputs), unset: the host rule
   int camera_vertex = -1;     // CRT_CAMERA_VERTEX: 0 never k_camera_vertex, 1 or unset wherever the plan's rule holds
+  int pixel_table = -1;       // CRT_PIXEL_TABLE: 0 never the per-pixel camera table, 1 or unset wherever a camera launch runs
+  int cull_root_lds = -1;     // CRT_CULL_ROOT_LDS: 0 the camera launch's cull holds the root in registers, 1 or unset reads it from LDS
   int noclassify_from = 1 << 30, tail_from = 12, lanes = 4, grid_mult = 0;
   size_t max_batch_slots = 0, lane_min_paths = (size_t)96 << 20, stage_min_paths = (size_t)96 << 20;
 };

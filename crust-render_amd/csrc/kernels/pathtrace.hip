@@ -31,6 +31,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "camera_pixel.hip.h"
 #include "shade.hip.h"
 #include "traverse_camera.hip.h"
 #include "traverse_pool.hip.h"
@@ -55,6 +56,7 @@ namespace {
 #endif
 
 enum { K_CAMERA = 0, K_PATH = 1, K_TIME = 2 };                 // tracer.rs:20-22 (off root)
+static_assert(K_CAMERA == kDomainCamera && K_PATH == kDomainPath, "camera_pixel.hip.h derives the same domains");
 // (the domains off a vertex, K_NEE .. K_VOLUME, and the roulette constants: vertex_simple.hip.h)
 constexpr uint32_t kFilmTarget = 0x80000000u;
 constexpr uint32_t kPrevValid = 1u << 16, kPrevDelta = 1u << 17;
@@ -445,6 +447,55 @@ __device__ __forceinline__ size_t camera_slot_sample(size_t k) {
   return ((k / kBlock) * (size_t)gridDim.x + blockIdx.x) * kBlock + (k % kBlock);
 }
 
+// camera_sample's second form (camera_pixel.hip.h): what depends on the pixel alone comes from the renderer's table, one
+// record per owned-pixel slot, and (pix, sl) from the caller's sample cursor. The arithmetic left — the index scramble,
+// the Sobol draw, the filter offsets, the ray — is the first form's on the same words, so the two return the same bits.
+// Static pinhole batches only (the camera launches' plans): no K_TIME draw.
+// The record's two 16-byte halves come from pixel_rec_load, which the camera launches issue a round ahead: a lane's next
+// pixel slot is its cursor's (always below n_act, past the batch's end too), so the load flies behind the trace of the
+// current ray instead of heading a round trip at the top of every round.
+__device__ __forceinline__ void pixel_rec_load(const Params &P, const PixelRec *table, uint32_t pix, uint4 &r0, uint4 &r1) {
+  const uint4 *rec = reinterpret_cast<const uint4 *>(table + (P.active ? P.active[pix] : pix));
+  r0 = rec[0]; r1 = rec[1];
+}
+__device__ __forceinline__ CameraSample camera_sample_table(const Params &P, uint4 r0, uint4 r1, uint32_t pix, uint32_t sl,
+                                                            uint32_t sample_begin, const uint32_t *sobol_tab) {
+  CameraSample cs;
+  cs.pix = pix; cs.sl = sl;
+  const uint32_t seed[5] = {r0.z, r0.w, r1.x, r1.y, r1.z};
+  float cam[4];
+  draw_sample4_seeded(sample_begin + sl, seed, cam, sobol_tab);
+  const float fx = filter_offset(P.filter_kind, P.filter_radius, cam[0]);
+  const float fy = filter_offset(P.filter_kind, P.filter_radius, cam[1]);
+  const float u = (__uint_as_float(r0.x) + fx) / (float)P.width;
+  const float v = (__uint_as_float(r0.y) + fy) / (float)P.height;
+  cs.time = 0.0f;
+  camera_get_ray(P.camera, u, v, cam[2], cam[3], cs.o, cs.d);
+  cs.pattern = r1.w;
+  return cs;
+}
+// The root cull's predicate on the root as stage_nodes laid it out in the LDS window (seven 16-byte parts: three of
+// lower bounds, three of upper bounds, the child words — WideNode's own order): node_touched on the same 28 words.
+__device__ __forceinline__ bool root_touched_lds(const uint32_t *node, V3 o, V3 d) {
+  const float4 *nb = reinterpret_cast<const float4 *>(node);
+  float bmin[3][4], bmax[3][4];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float4 lo = nb[a], hi = nb[3 + a];
+    bmin[a][0] = lo.x; bmin[a][1] = lo.y; bmin[a][2] = lo.z; bmin[a][3] = lo.w;
+    bmax[a][0] = hi.x; bmax[a][1] = hi.y; bmax[a][2] = hi.z; bmax[a][3] = hi.w;
+  }
+  const uint4 ch = *reinterpret_cast<const uint4 *>(nb + 6);
+  const uint32_t child[4] = {ch.x, ch.y, ch.z, ch.w};
+  return node_touched(bmin, bmax, child, o.x, o.y, o.z, d.x, d.y, d.z, 0.001f, CRT_INF);
+}
+// One record per owned-pixel slot, once per renderer (crt_renderer_new): the frame number and the pixel list never change.
+__global__ void k_fill_pixel_table(const uint32_t *pixel_index, uint32_t n_pix, uint32_t width, int frame, PixelRec *table) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pix) return;
+  table[i] = pixel_record(pixel_index[i], width, frame);
+}
+
 // A compact camera path (Params::cam_compact) read back: direction and pattern from plane `a`, origin = the pinhole
 // camera's (camera_get_ray with no lens offset: origin + 0), pixel and sample from the slot's sample number (< 2^31:
 // ensure_buffers). D = plane d's words as generate would have written them — under the root cull (cam_compact == 2) the
@@ -615,15 +666,22 @@ __global__ __launch_bounds__(kBlock) void k_generate(Params P, PathSoA S, Counte
 // stack limit below kCamStack (tests of the list and of the deferred instance).
 constexpr int kCamLdsDwords = kCamWindow * kLdsNodeStride + kCamStack * kBlock;
 static_assert((kSobolLdsWords + kCamLdsDwords) * 4 + 512 <= 40 * 1024, "four workgroups of k_camera per CU");
+// TABLE: the sample loop reads the renderer's per-pixel table and steps a sample cursor (camera_pixel.hip.h,
+// camera_sample_table) instead of calling camera_sample on the sample number; false: the loop as it was.
+// ROOT_LDS: the cull reads the root node from the staged window every round (root_touched_lds) instead of holding its 28
+// words in scalar registers the kernel parks in VGPR lanes; the plan asks for it only where the root is node 0, which
+// stage_nodes always stages.
+template <bool TABLE, bool ROOT_LDS>
 __global__ __launch_bounds__(kBlock, 4) void k_camera(Params P, PathSoA S, uint32_t *defer_plane, HitSoA H, Counters *C,
-                                                      uint32_t sample_begin, uint32_t n_samples, float4 *staging, uint32_t mode) {
+                                                      uint32_t sample_begin, uint32_t n_samples, float4 *staging, uint32_t mode,
+                                                      const PixelRec *pixel_table) {
   __shared__ uint32_t sobol_tab[kSobolLdsWords];
   __shared__ __attribute__((aligned(16))) uint32_t cam_lds[kCamLdsDwords];
   __shared__ uint32_t cam_ctr[3];  // survivors appended (live slots) | camera rays finished here | rays left to the first extend
   const bool cull = P.root_cull != 0;  // uniform
-  float bmin[3][4], bmax[3][4];
-  uint32_t child[4];
-  {
+  float bmin[3][4] = {}, bmax[3][4] = {};
+  uint32_t child[4] = {};
+  if (!ROOT_LDS) {
     const WideNode &root = P.scene.nodes[P.scene.root];
 #pragma unroll
     for (int a = 0; a < 3; a++)
@@ -646,18 +704,33 @@ __global__ __launch_bounds__(kBlock, 4) void k_camera(Params P, PathSoA S, uint3
   uint32_t *list = defer_plane + 4 * seg0;  // 4 * seg_cap words of the segment's plane; at most seg_cap are used
   const V3 cam_o = ld3(P.camera.origin) + splat(0.0f);  // the pinhole camera's origin, as the compact form's readers take it
   uint32_t n_culled = 0, n_valid = 0;
+  // TABLE: this lane's pixel slot and sample, round by round, and the pixel's record, loaded a round ahead
+  SampleCursor at_g = {0, 0, 0, 0};
+  uint4 rec0 = make_uint4(0, 0, 0, 0), rec1 = make_uint4(0, 0, 0, 0);
+  if (TABLE) {
+    at_g = sample_cursor(camera_slot_sample(threadIdx.x), (unsigned long long)gridDim.x * kBlock, P.n_act);
+    pixel_rec_load(P, pixel_table, at_g.pix, rec0, rec1);
+  }
   for (size_t k0 = 0; k0 < P.seg_cap; k0 += kBlock) {  // uniform: seg_cap is a multiple of the workgroup's width
     if (camera_slot_sample(k0) >= total) break;        // uniform
     const size_t g = camera_slot_sample(k0 + threadIdx.x);
+    const uint32_t t_pix = at_g.pix, t_sl = at_g.sl;
+    const uint4 t_rec0 = rec0, t_rec1 = rec1;
+    if (TABLE) {  // the next round's record: its slot is below n_act whether or not that round exists
+      sample_cursor_next(at_g, P.n_act);
+      pixel_rec_load(P, pixel_table, at_g.pix, rec0, rec1);
+    }
     CameraSample cs;
     cs.o = splat(0.0f); cs.d = splat(0.0f); cs.time = 0.0f; cs.pattern = 0; cs.pix = 0; cs.sl = 0;
     bool keep = false;
     if (g < total) {
-      cs = camera_sample(P, g, sample_begin, sobol_tab);
+      if (TABLE) cs = camera_sample_table(P, t_rec0, t_rec1, t_pix, t_sl, sample_begin, sobol_tab);
+      else cs = camera_sample(P, g, sample_begin, sobol_tab);
       keep = true;
       n_valid = (uint32_t)(k0 + threadIdx.x) + 1;
       if (cull) {  // uniform
-        keep = node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);
+        keep = ROOT_LDS ? root_touched_lds(lds_nodes + (size_t)P.scene.root * kLdsNodeStride, cs.o, cs.d)
+                        : node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);
         if (!keep) {  // tracer.rs:1321-1342 with L = 0, beta = 1: the first shade's miss step
           const V3 L = escaped_to_sky(cs.d, splat(1.0f), splat(0.0f));
           st_nt(&staging[cs.sl * P.n_act + cs.pix], make_float4(L.x, L.y, L.z, 0.0f));
@@ -1785,17 +1858,19 @@ __global__ __launch_bounds__(kBlock, CRT_SHADE_WIDE_WAVES) void k_shade_pipe(Par
 // first shade would have added them. LDS: the material table (at most kPipeMatMax records, as k_shade_pipe stages it)
 // beside k_camera's Sobol tables, node window and stacks — the window keeps its kCamWindow strides.
 static_assert((kSobolLdsWords + kCamLdsDwords + kPipeMatMax * kMatDwords) * 4 + 512 <= 40 * 1024, "four workgroups of k_camera_vertex per CU");
-template <bool DRV>
+// TABLE, ROOT_LDS: as k_camera's — the per-pixel table and the sample cursor in the sample loop; the cull's root from LDS.
+template <bool DRV, bool TABLE, bool ROOT_LDS>
 __global__ __launch_bounds__(kBlock, 4) void k_camera_vertex(Params P, PathSoA S, PathSoA N, Counters *C, uint32_t sample_begin,
-                                                             uint32_t n_samples, float4 *staging, uint32_t mode, int slim_out) {
+                                                             uint32_t n_samples, float4 *staging, uint32_t mode, int slim_out,
+                                                             const PixelRec *pixel_table) {
   __shared__ uint32_t sobol_tab[kSobolLdsWords];
   __shared__ __attribute__((aligned(16))) uint32_t cam_lds[kCamLdsDwords];
   __shared__ __attribute__((aligned(16))) uint32_t mat_lds[kPipeMatMax * kMatDwords];
   __shared__ uint32_t cam_ctr[4];  // rays left to the first extend | camera rays that escaped here | survivors | vertices
   const bool cull = P.root_cull != 0;  // uniform
-  float bmin[3][4], bmax[3][4];
-  uint32_t child[4];
-  {
+  float bmin[3][4] = {}, bmax[3][4] = {};
+  uint32_t child[4] = {};
+  if (!ROOT_LDS) {
     const WideNode &root = P.scene.nodes[P.scene.root];
 #pragma unroll
     for (int a = 0; a < 3; a++)
@@ -1824,9 +1899,22 @@ __global__ __launch_bounds__(kBlock, 4) void k_camera_vertex(Params P, PathSoA S
   const size_t seg0 = (size_t)blockIdx.x * kBins * P.seg_cap;
   const V3 cam_o = ld3(P.camera.origin) + splat(0.0f);  // the pinhole camera's origin, as the compact form's readers take it
   uint32_t n_escaped = 0, n_vertices = 0;
+  // TABLE: this lane's pixel slot and sample, round by round, and the pixel's record, loaded a round ahead
+  SampleCursor at_g = {0, 0, 0, 0};
+  uint4 rec0 = make_uint4(0, 0, 0, 0), rec1 = make_uint4(0, 0, 0, 0);
+  if (TABLE) {
+    at_g = sample_cursor(camera_slot_sample(threadIdx.x), (unsigned long long)gridDim.x * kBlock, P.n_act);
+    pixel_rec_load(P, pixel_table, at_g.pix, rec0, rec1);
+  }
   for (size_t k0 = 0; k0 < P.seg_cap; k0 += kBlock) {  // uniform: seg_cap is a multiple of the workgroup's width
     if (camera_slot_sample(k0) >= total) break;        // uniform
     const size_t g = camera_slot_sample(k0 + threadIdx.x);
+    const uint32_t t_pix = at_g.pix, t_sl = at_g.sl;
+    const uint4 t_rec0 = rec0, t_rec1 = rec1;
+    if (TABLE) {  // the next round's record: its slot is below n_act whether or not that round exists
+      sample_cursor_next(at_g, P.n_act);
+      pixel_rec_load(P, pixel_table, at_g.pix, rec0, rec1);
+    }
     CameraSample cs;
     cs.o = splat(0.0f); cs.d = splat(0.0f); cs.time = 0.0f; cs.pattern = 0; cs.pix = 0; cs.sl = 0;
     int res = CAM_MISS;
@@ -1834,10 +1922,13 @@ __global__ __launch_bounds__(kBlock, 4) void k_camera_vertex(Params P, PathSoA S
     VertexOut v;
     v.origin = splat(0.0f); v.dir = splat(0.0f); v.beta = splat(1.0f); v.L = splat(0.0f); v.delta = false;
     if (g < total) {
-      cs = camera_sample(P, g, sample_begin, sobol_tab);
+      if (TABLE) cs = camera_sample_table(P, t_rec0, t_rec1, t_pix, t_sl, sample_begin, sobol_tab);
+      else cs = camera_sample(P, g, sample_begin, sobol_tab);
       valid = true;
       bool keep = true;
-      if (cull) keep = node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);  // uniform
+      if (cull)  // uniform
+        keep = ROOT_LDS ? root_touched_lds(lds_nodes + (size_t)P.scene.root * kLdsNodeStride, cs.o, cs.d)
+                        : node_touched(bmin, bmax, child, cs.o.x, cs.o.y, cs.o.z, cs.d.x, cs.d.y, cs.d.z, 0.001f, CRT_INF);
       float t = 0.0f;
       uint32_t prim = kInvalid;
       if (keep)
@@ -2101,7 +2192,10 @@ using ExtendDeferredFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int,
 using PathFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, float4 *, uint32_t, uint32_t, uint32_t, int);
 using ShadeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int);
 using ShadePipeFn = void (*)(Params, PathSoA, PathSoA, HitSoA, Counters *, int, float4 *, int, uint32_t, int);
-using CameraVertexFn = void (*)(Params, PathSoA, PathSoA, Counters *, uint32_t, uint32_t, float4 *, uint32_t, int);
+using CameraVertexFn = void (*)(Params, PathSoA, PathSoA, Counters *, uint32_t, uint32_t, float4 *, uint32_t, int, const PixelRec *);
+using CameraFn = void (*)(Params, PathSoA, uint32_t *, HitSoA, Counters *, uint32_t, uint32_t, float4 *, uint32_t, const PixelRec *);
+template <bool TABLE, bool ROOT_LDS>
+static CameraVertexFn camera_vertex_fn(bool drv) { return drv ? k_camera_vertex<true, TABLE, ROOT_LDS> : k_camera_vertex<false, TABLE, ROOT_LDS>; }
 using ShadowFn = void (*)(Params, PathSoA, ShadowSoA, Counters *, float4 *, CrtTravStats *);
 using ShadeVolFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, uint32_t *);
 template <class Fn>
@@ -2208,7 +2302,10 @@ struct Renderer {
   CrtLight *d_lights = nullptr;
   std::vector<std::shared_ptr<void>> environments;  // what the mapped domes of the light list name (Params::envs is set iff any)
   uint32_t *d_pixels = nullptr;
-  int grid = 768;          // of the last batch; the film kernels use it too
+  // One PixelRec per owned-pixel slot (kernels/camera_pixel.hip.h), filled once at creation where a plan of this renderer
+  // can read it; nullptr: none was built (no such plan, CRT_PIXEL_TABLE=0, or no memory — the computed form then runs).
+  PixelRec *d_pixel_table = nullptr;
+  int grid = 768;         // of the last batch; the film kernels use it too
   hipStream_t last_stream = nullptr;
   bool profile = false;
   struct Ev { hipEvent_t a, b; int cls; };
@@ -2239,6 +2336,7 @@ struct Renderer {
     if (d_count) (void)hipFree(d_count);
     if (d_lights) (void)hipFree(d_lights);
     if (d_pixels) (void)hipFree(d_pixels);
+    if (d_pixel_table) (void)hipFree(d_pixel_table);
   }
 
   void drain_events() {
@@ -2395,18 +2493,47 @@ struct Renderer {
   // The launch plan of one lane's batch of n_samples (crt_internal.h, plan_launches), its grid and segment size, and its
   // buffers (they grow when a batch needs more slots than any before). Sets last_plan / grid for the launches that
   // follow, and p.seg_cap, p.cam_compact, p.root_cull.
-  int plan_lane(Lane &B, Params &p, uint32_t n_samples, bool stats) {
-    const size_t total = (size_t)p.n_act * n_samples;
-    in.total = total;
-    in.stats = stats;
-    // from P at every plan, so that nothing set after creation leaves the plan stale; the engine choice, mats_kind and
-    // the root's miss share are derived at creation from what no entry point changes (the image, the table, the camera)
+  // from P at every plan, so that nothing set after creation leaves the plan stale; the engine choice, mats_kind and
+  // the root's miss share are derived at creation from what no entry point changes (the image, the table, the camera)
+  void plan_inputs_from_params() {
     in.scene = P.scene;
     in.n_lights = P.n_lights; in.has_inf_lights = P.has_inf_lights != 0; in.has_env = P.envs != nullptr; in.strategy = P.strategy;
     in.has_motion = P.has_motion != 0; in.lens = P.camera.lens_radius > 0.0f;
     in.mat_index = P.mat_index != nullptr; in.partition = P.partition; in.n_materials = P.n_materials; in.max_depth = P.max_depth;
     in.class_stats = P.class_stats;
     in.volumes = volumes != nullptr;
+  }
+  // The per-pixel camera table (kernels/camera_pixel.hip.h), at creation: built where the plan of a large batch of this
+  // renderer names it — asked of plan_launches itself, so the rule stays in one place. No memory for it (32 bytes per
+  // owned pixel) or a frame wider than the records' float coordinates hold: no table, and every plan runs the computed form.
+  void build_pixel_table() {
+    in.pixel_table_ready = false;
+    if (in.pixel_table_knob == 0 || P.width > kPixelTableMaxExtent || P.height > kPixelTableMaxExtent) return;
+    plan_inputs_from_params();
+    PlanInputs q = in;
+    q.total = ~(size_t)0 >> 1; q.stats = false; q.partial_active = false; q.pixel_table_ready = true;
+    LaunchPlan trial;
+    if (plan_launches(q, trial) != CRT_OK || !trial.pixel_table) return;
+    if (hipMalloc(&d_pixel_table, (size_t)P.n_pix * sizeof(PixelRec)) != hipSuccess) {
+      (void)hipGetLastError();  // not an error: the computed form
+      d_pixel_table = nullptr;
+      return;
+    }
+    hipLaunchKernelGGL(k_fill_pixel_table, dim3((P.n_pix + 255) / 256), dim3(256), 0, nullptr, P.pixel_index, P.n_pix, P.width,
+                       P.frame, d_pixel_table);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {  // filled before any lane's stream reads it
+      (void)hipFree(d_pixel_table);
+      d_pixel_table = nullptr;
+      return;
+    }
+    in.pixel_table_ready = true;
+  }
+
+  int plan_lane(Lane &B, Params &p, uint32_t n_samples, bool stats) {
+    const size_t total = (size_t)p.n_act * n_samples;
+    in.total = total;
+    in.stats = stats;
+    plan_inputs_from_params();
     in.partial_active = p.active != nullptr;
     if (in.volumes && stats) {
       set_error_text("render refused: the stats build does not run volume renders");
@@ -2488,16 +2615,22 @@ struct Renderer {
     // — or k_camera_vertex: the same with the first vertex shaded behind the trace; its survivors are in S[1] already, and
     // the first extend and the first shade (append mode, bit 1 of `first`) see only the rays it deferred, which lie in S[0]
     // in the compact form with plane d whatever the cull says
+    const PixelRec *pixel_table = plan.pixel_table ? d_pixel_table : nullptr;  // plan.pixel_table: the renderer holds one
+    if (plan.pixel_table && !pixel_table) return CRT_ERR_UNSUPPORTED;
     Params p0 = p;  // the launches of bounce 0 behind k_camera_vertex
     if (plan.camera_vertex) {
       p0.cam_compact = 2;
       const uint32_t nx = 1;
       const int slim_out = (shade_slim && nx <= P.max_depth && nx < plan.tail_at && (int)nx < plan.noclassify_from) ? 1 : 0;
-      const CameraVertexFn fn = plan.shade_early.arg[0] ? k_camera_vertex<true> : k_camera_vertex<false>;
-      timed(3, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], C, sample_begin, n_samples, staging, plan.camera_mode, slim_out); });
-    } else if (plan.camera_trace)
-      timed(3, st, [&] { hipLaunchKernelGGL(k_camera, dim3(grid), dim3(kBlock), 0, st, p, S[0], reinterpret_cast<uint32_t *>(S[1].a), H, C, sample_begin, n_samples, staging, plan.camera_mode); });
-    else
+      const bool drv = plan.shade_early.arg[0] != 0;
+      const CameraVertexFn fn = plan.pixel_table ? (plan.cull_root_lds ? camera_vertex_fn<true, true>(drv) : camera_vertex_fn<true, false>(drv))
+                                                 : (plan.cull_root_lds ? camera_vertex_fn<false, true>(drv) : camera_vertex_fn<false, false>(drv));
+      timed(3, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[0], S[1], C, sample_begin, n_samples, staging, plan.camera_mode, slim_out, pixel_table); });
+    } else if (plan.camera_trace) {
+      const CameraFn fn = plan.pixel_table ? (plan.cull_root_lds ? k_camera<true, true> : k_camera<true, false>)
+                                           : (plan.cull_root_lds ? k_camera<false, true> : k_camera<false, false>);
+      timed(3, st, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, st, p, S[0], reinterpret_cast<uint32_t *>(S[1].a), H, C, sample_begin, n_samples, staging, plan.camera_mode, pixel_table); });
+    } else
       timed(3, st, [&] { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, st, p, S[0], C, sample_begin, n_samples, staging); });
     int cur = 0;
     for (uint32_t it = 0; it <= P.max_depth; it++) {
@@ -2757,6 +2890,9 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   in.shade_wide = knobs.shade_wide;
   in.force_fused = knobs.fused;
   in.stage_min_paths = knobs.stage_min_paths;
+  in.pixel_table_knob = knobs.pixel_table;
+  in.cull_root_lds_knob = knobs.cull_root_lds;
+  r.build_pixel_table();  // behind every input of the plan above
   r.max_batch_slots = knobs.max_batch_slots;
   r.n_lanes = knobs.lanes < 1 ? 1 : (knobs.lanes > Renderer::kMaxLanes ? Renderer::kMaxLanes : knobs.lanes);
   r.lane_min_paths = knobs.lane_min_paths;
@@ -2931,7 +3067,8 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   const LaunchPlan &plan = r->r.last_plan;  // every bit below is a per-stage one: plan_launches sets none of them on a fused plan
   out[0] = plan.fused ? 1u : 0u;
   out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u) |
-           (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u) | (plan.camera_vertex ? 64u : 0u);
+           (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u) | (plan.camera_vertex ? 64u : 0u) |
+           (plan.pixel_table ? 128u : 0u) | (plan.cull_root_lds ? 256u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

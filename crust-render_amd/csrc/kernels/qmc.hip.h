@@ -91,6 +91,33 @@ __device__ __forceinline__ void draw_sample4(Sampler s, float out[4], const uint
     out[d] = unit_f32(x);
   }
 }
+// The five Owen-scramble seeds draw_sample4 hashes from a domain's pattern — the index scramble's, then one per
+// dimension — and the draw itself from those seeds. The seeds depend on the pattern alone, so a caller whose pattern
+// outlives its index (a pixel's K_CAMERA domain: camera_pixel.hip.h) keeps them and calls the second form.
+__device__ __forceinline__ void owen_seeds(uint32_t pattern, uint32_t seed[5]) {
+  seed[0] = pcg_hash(pattern);
+#pragma unroll
+  for (int d = 0; d < 4; d++) seed[d + 1] = pcg_hash(pattern + (uint32_t)d + 1u);
+}
+__device__ __forceinline__ void draw_sample4_seeded(uint32_t index, const uint32_t seed[5], float out[4], const uint32_t *tab) {
+  const uint32_t idx = owen(index, seed[0]);
+  const uint32_t b0 = idx & 255u, b1 = (idx >> 8) & 255u, b2 = (idx >> 16) & 255u, b3 = idx >> 24;
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    uint32_t x;
+    if (d == 0) {
+      x = __brev(idx);  // dimension 0's matrix is the identity on reversed bits
+    } else {
+      const uint32_t *t = tab + (d - 1) * 1024;
+      x = t[b0] ^ t[256 + b1] ^ t[512 + b2] ^ t[768 + b3];
+    }
+    x = owen(x, seed[d + 1]);
+    out[d] = unit_f32(x);
+  }
+}
+// (draw_sample4 above keeps its own text: written as owen_seeds + draw_sample4_seeded it compiles to one instruction more
+// in every kernel that draws, profiles/README.md. The words are integer hashes of the same inputs either way;
+// tests/test_pixel_table_host.py compares the two forms and the oracle's bit for bit.)
 __device__ __forceinline__ float draw_rnd1(Sampler s) {
   return unit_f32(pcg_hash(s.pattern ^ (s.index * 0x9e3779b9u + 0x7f4a7c15u)));
 }

@@ -240,6 +240,8 @@ Knobs read_knobs() {
   if (num("CRT_SLIM_STATE", v)) k.slim_state = v != 0;
   if (num("CRT_CAMERA_TRACE", v)) k.camera_trace = (v >= 0 && v <= 3) ? (int)v : 1;
   if (num("CRT_CAMERA_VERTEX", v)) k.camera_vertex = v != 0 ? 1 : 0;
+  if (num("CRT_PIXEL_TABLE", v)) k.pixel_table = v != 0 ? 1 : 0;
+  if (num("CRT_CULL_ROOT_LDS", v)) k.cull_root_lds = v != 0 ? 1 : 0;
   if (num("CRT_FUSED", v)) k.fused = v != 0;
   if (num("CRT_NOCLASSIFY_FROM", v)) k.noclassify_from = (int)std::min<long long>(std::max<long long>(v, 0), 1 << 30);
   if (num("CRT_TAIL_FROM", v)) k.tail_from = (int)std::min<long long>(std::max<long long>(v, 0), 1 << 30);

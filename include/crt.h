@@ -462,7 +462,12 @@ int crt_renderer_shade_class_stats(CrtRenderer *r, int enable, uint64_t out_wave
  * when one launch generated, culled and traced the batch's camera rays and the first extend only picked up the rays that
  * launch deferred (unlit pinhole scenes on the flat four-wave engine; CRT_CAMERA_TRACE=0: never), | 64 when that launch
  * also shaded the first vertex of every camera path it traced, so that the first extend and the first shade launch ran
- * over the deferred rays alone (with | 2 and | 32, a depth limit of at least 1; CRT_CAMERA_VERTEX=0: never);
+ * over the deferred rays alone (with | 2 and | 32, a depth limit of at least 1; CRT_CAMERA_VERTEX=0: never), | 128 when
+ * that launch read what a camera sample owes to its pixel alone (coordinates, the camera domain's scramble seeds, the
+ * path domain's pattern) from a 32-byte record per owned pixel that the renderer filled at creation, and stepped each
+ * lane's (pixel, sample) pair from round to round instead of dividing (with | 32; CRT_PIXEL_TABLE=0: never), | 256 when
+ * that launch's root cull read the root node from the launch's LDS window instead of holding it in registers (with | 4
+ * and | 32, the image's root at node 0; CRT_CULL_ROOT_LDS=0: never);
  * out[2] = workgroups (= queue segments) per launch.
  * The renderer takes the per-stage form for batches of >= 96 Mi paths and the fused kernel for smaller ones and for the
  * tail of a large one. Environment CRT_FUSED / CRT_WIDE / CRT_STAGE_MIN_PATHS / CRT_GRID_MULT override. */
