@@ -206,6 +206,7 @@ struct DevInstanceMotion {
 // Entries of `indices` (a leaf's scalar list): primitive index, or kIndexInstance | instance slot. Instance slots
 // follow the order of the scalar lists, so the placements of one leaf, and of neighbouring leaves, share cache lines.
 constexpr uint32_t kIndexInstance = 0x80000000u;
+namespace dev { constexpr int kBlock = 256; }  // threads per workgroup (4 waves): the kernels' launch bounds and the hosts' launches
 
 struct DevScene {
   const WideNode *nodes;
@@ -311,7 +312,7 @@ inline bool wide_split(const DevScene &s, bool renderer = false) {
 #define CRT_POOL_STACK_WIDE 3   // four-wave kernels
 #endif
 
-// Which instance of the traversal engine runs an image. THE one decision: the renderer (pathtrace.hip), the batched and
+// Which instance of the traversal engine runs an image. THE one decision: the renderer (render.cpp), the batched and
 // the single-ray queries (traverse.hip) and the host-only crt_scene_engine_select all call select_engine, and every
 // launch goes through the EngineSelect it returns — an engine instance never meets an image form it was not built for
 // (rounds 2 and 3 each lost a GPU box to exactly that: profiles/README.md, "The r02f abort", "The r03w fault").
@@ -375,12 +376,13 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
 // ---------------------------------------------------------------------------------------------
 // The renderer's launch plan: which kernel instances run one batch. plan_launches decides it once per batch from a
 // PlanInputs — every fact the choice depends on, as plain values — and names each instance by an InstanceKey;
-// kernels/pathtrace.hip holds the table {key, kernel pointer} built from the lists below and launches through what it
-// finds there. A new instance is one row of a list and one line of policy in plan_launches. Plain C++17, no HIP names:
+// kernels/pathtrace.hip holds the table {key, kernel pointer} built from the lists below (resolve_kernels,
+// render_kernels.h), and render.cpp launches through what that finds there. A new instance is one row of a list and one
+// line of policy in plan_launches. Plain C++17, no HIP names:
 // tests/test_launch_plan.py sweeps the function on the CPU.
 // ---------------------------------------------------------------------------------------------
 enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC,
-                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME, KF_EXTEND_DEFERRED };
+                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME, KF_EXTEND_DEFERRED, KF_CAMERA, KF_CAMERA_VERTEX };
 struct InstanceKey {  // a kernel template and its arguments, in the template's order (bools as 0 / 1)
   uint8_t family = KF_NONE;
   uint8_t arg[5] = {0, 0, 0, 0, 0};
@@ -448,6 +450,16 @@ struct InstanceKey {  // a kernel template and its arguments, in the template's 
   X(SHADE_VOL, k_shade_vol, 0, 0, false) X(SHADE_VOL, k_shade_vol, 0, 0, true) X(SHADE_VOL, k_shade_vol, 0, 1, true) X(SHADE_VOL, k_shade_vol, 0, 2, true) \
   X(SHADE_VOL, k_shade_vol, 1, 0, false) X(SHADE_VOL, k_shade_vol, 1, 0, true) X(SHADE_VOL, k_shade_vol, 1, 1, true) X(SHADE_VOL, k_shade_vol, 1, 2, true) \
   X(SHADE_VOL, k_shade_vol, 2, 0, false) X(SHADE_VOL, k_shade_vol, 2, 0, true) X(SHADE_VOL, k_shade_vol, 2, 1, true) X(SHADE_VOL, k_shade_vol, 2, 2, true)
+// The camera launches (LaunchPlan::camera_trace / camera_vertex): TABLE = the sample loop reads the per-pixel table,
+// ROOT_LDS = the cull reads the root from the LDS window, DRV = shade_early's table. Lists of their own: a plan names
+// the instance through camera_key().
+#define CRT_INSTANCES_CAMERA(X) /* k_camera<TABLE, ROOT_LDS> */ \
+  X(CAMERA, k_camera, false, false) X(CAMERA, k_camera, false, true) X(CAMERA, k_camera, true, false) X(CAMERA, k_camera, true, true)
+#define CRT_INSTANCES_CAMERA_VERTEX(X) /* k_camera_vertex<DRV, TABLE, ROOT_LDS> */ \
+  X(CAMERA_VERTEX, k_camera_vertex, false, false, false) X(CAMERA_VERTEX, k_camera_vertex, false, false, true) \
+  X(CAMERA_VERTEX, k_camera_vertex, false, true, false) X(CAMERA_VERTEX, k_camera_vertex, false, true, true) \
+  X(CAMERA_VERTEX, k_camera_vertex, true, false, false) X(CAMERA_VERTEX, k_camera_vertex, true, false, true) \
+  X(CAMERA_VERTEX, k_camera_vertex, true, true, false) X(CAMERA_VERTEX, k_camera_vertex, true, true, true)
 
 // What the choice of a batch's kernels depends on. The renderer keeps one: the engine choice, the A/B knobs and the
 // build's switches are filled when it is created; what its Params hold, and the per-batch fields, before every plan.
@@ -478,7 +490,7 @@ struct PlanInputs {
   bool no_emitter = false;        // no record of the material table can emit (table_has_no_emitter, at creation)
   bool cam_compact_ok = true;     // CRT_CAM_COMPACT
   int root_cull_knob = -1;        // CRT_ROOT_CULL: 0 = generate never finishes a camera ray, 1 = wherever the rule allows (A/B, tests)
-  float root_miss_share = 0.0f;   // share of a coarse grid of camera rays that misses every child of the root (pathtrace.hip)
+  float root_miss_share = 0.0f;   // share of a coarse grid of camera rays that misses every child of the root (render.cpp)
   // A volume aggregate is bound (crt_renderer_set_volumes): the batch runs one launch per stage whatever its size, with
   // k_volume between extend and shade, the VOL shade instances and — where the shadow stage runs — k_shadow_volume ahead
   // of k_shadow. false: exactly the plan of a renderer that never heard of volumes.
@@ -491,7 +503,7 @@ struct PlanInputs {
   size_t total = 0;               // paths of the batch
   bool stats = false;             // the stats build (crt_render_samples_stats)
   bool partial_active = false;    // adaptive stopping with an active list shorter than the frame (Params::active)
-  // the build's switches that gate forms (kernels/pathtrace.hip)
+  // the build's switches that gate forms (kernels/pathtrace.hip, handed over in render_kernels.h's KernelBuild)
   bool cam_compact_build = true, wide_direct_build = CRT_WIDE_DIRECT_BUILD != 0, nopk_build = CRT_NOPK_BUILD != 0;
   bool shade_pipe_build = true, root_cull_build = true;
   int pipe_mat_max = 0;
@@ -539,6 +551,17 @@ inline bool table_has_no_emitter(const CrtMaterial *m, size_t n) {
   }
   return true;
 }
+// Material class = which arms of the vertex code a hit on this material runs (openpbr.rs:1026-1136 dispatches one of
+// five lobes + thin film + dispersion per lane; rt_world.rs:219-231 binds the material per geom_id). Waves whose
+// 64 vertices share a class skip the other classes' lobes with a scalar branch instead of idling through them.
+//   0 emissive (Emissive: emission only, never scatters)      1 base: diffuse + specular (dielectric or metal)
+//   2 layered: coat and / or fuzz and / or thin film on top    3 transmissive or subsurface (refraction, interior medium)
+inline uint8_t material_class(const CrtMaterial &m) {
+  if (m.kind == CRT_MAT_EMISSIVE) return 0;
+  if (m.transmission_weight > 0.0f || m.subsurface_weight > 0.0f) return 3;
+  if (m.coat_weight > 0.0f || m.fuzz_weight > 0.0f || m.thin_film_weight > 0.0f) return 2;
+  return 1;
+}
 struct LaunchPlan {
   bool fused = true;              // one k_path launch for the whole path loop; otherwise one launch per stage and bounce
   bool wide = false;              // per-stage: the four-wave traversal kernels
@@ -551,7 +574,7 @@ struct LaunchPlan {
   InstanceKey path, extend, shade, shade_early, shadow_key;  // path: the fused launch or the tail; shade_early: the
                                   // pipelined instance, which runs the bounces before noclassify_from; none = not launched
   bool shade_piped() const { return !shade_early.none(); }
-  // The pipelined kernel's launches hand each other the SLIM path state (kernels/pathtrace.hip, PathSoA): three planes,
+  // The pipelined kernel's launches hand each other the SLIM path state (render_kernels.h, PathSoA): three planes,
   // without the words every live path of a launch shares and without the radiance, which is +0 where nothing emits. A
   // field of its own — shade_early names the same instance whatever this says; render_lane launches shade_slim_key().
   // Volume renders (PlanInputs::volumes): k_volume runs between extend and shade of every bounce, k_shadow_volume ahead
@@ -585,6 +608,19 @@ struct LaunchPlan {
   // The camera launch's cull reads the root from the staged window (k_camera / k_camera_vertex, ROOT_LDS): only where
   // the root is node 0, the first node stage_nodes copies.
   bool cull_root_lds = false;
+  // The camera launch's instance: k_camera_vertex<shade_early's DRV, TABLE, ROOT_LDS> or k_camera<TABLE, ROOT_LDS>;
+  // none: the batch starts with k_generate.
+  InstanceKey camera_key() const {
+    InstanceKey k;
+    if (camera_vertex) {
+      k.family = KF_CAMERA_VERTEX;
+      k.arg[0] = shade_early.arg[0]; k.arg[1] = pixel_table; k.arg[2] = cull_root_lds;
+    } else if (camera_trace) {
+      k.family = KF_CAMERA;
+      k.arg[0] = pixel_table; k.arg[1] = cull_root_lds;
+    }
+    return k;
+  }
 };
 // The EngineSelect a traversal instance of width w amounts to on this image (0 = three waves, 1 = four, the flat engine
 // copy only, 2 = four, the direct copy only) — run_traversal picks the three-wave kernels' copy from the image.

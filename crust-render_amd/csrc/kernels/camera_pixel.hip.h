@@ -28,7 +28,6 @@ struct PixelRec {
   uint32_t path_pattern; // new_domain(root, K_PATH).pattern
 };
 static_assert(sizeof(PixelRec) == 32, "two 16-byte loads per camera sample");
-constexpr uint32_t kPixelTableMaxExtent = 1u << 24;
 
 // The root domain of a pixel's sampler (tracer.rs:543, :559-561): PathSampler::new(px, py, frame, index).new_domain(tile).
 __device__ __forceinline__ Sampler pixel_root(uint32_t px, uint32_t py, int frame, int index) {

@@ -33,7 +33,7 @@
 namespace crt {
 namespace dev {
 
-constexpr int kBlock = 256;       // threads per workgroup (4 waves)
+// (kBlock, the threads per workgroup: crt_internal.h — the host launchers read it too)
 // Top of the tree staged in LDS: the first nodes (breadth-first numbering), bounds + child words only (112 of the
 // node's 128 bytes: the traversal does not read `flags`). Two nodes' 16-byte reads collide on banks only when
 // their indices differ by a multiple of 16, the same as with any padded stride.

@@ -29,6 +29,15 @@ static const Named *find_key(const InstanceKey &k) {
     if (n.key == k) return &n;
   return nullptr;
 }
+// The lists a plan names through a derived key: camera_key(), extend_deferred_key(), shade_slim_key().
+static const Named kDerivedKeys[] = {CRT_INSTANCES_CAMERA(CRT_NAMED) CRT_INSTANCES_CAMERA_VERTEX(CRT_NAMED)
+                                     CRT_INSTANCES_EXTEND_DEFERRED(CRT_NAMED) CRT_INSTANCES_SHADE_PIPE_SLIM(CRT_NAMED)};
+static bool none_or_derived(const InstanceKey &k) {
+  if (k.none()) return true;
+  for (const Named &n : kDerivedKeys)
+    if (n.key == k) return true;
+  return false;
+}
 static std::string name_of(const InstanceKey &k) {
   if (k.none()) return "-";
   const Named *n = find_key(k);
@@ -151,6 +160,7 @@ static void check_case(const int *v, const DevScene &s, const EngineSelect &e) {
   REQUIRE(aggregate_check(q, pl));
   // 1. every key is an instance of this build
   for (const InstanceKey *k : keys) REQUIRE(k->none() || find_key(*k));
+  REQUIRE(none_or_derived(pl.camera_key()) && none_or_derived(pl.extend_deferred_key()) && none_or_derived(pl.shade_slim_key()));
   // 2. engine_accepts for the launched EngineSelect, per traversal instance, with the instance's own cold bits
   const int curve_bits = (int)(kColdAll | kColdCurve | kColdCubic);
   if (!pl.path.none()) REQUIRE(engine_accepts(engine_of_width(e, s, 0), s, pl.path.arg[2]));

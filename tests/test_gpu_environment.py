@@ -191,7 +191,7 @@ def _check_render(crt, desc, spp, name, want_class=None):
     err = np.abs(dimg - ref) / np.maximum(1.0, np.abs(ref))
     assert err.max() <= 1e-5, (name, err.max())  # the tolerance of test_forward_equals_reference_gather_within_float_association
     if want_class is not None:  # the look that selects the kernel instance is in the table the renderer was given
-        def cls(m):  # pathtrace.hip, material_class
+        def cls(m):  # crt_internal.h, material_class
             if m.kind == crt.MAT_EMISSIVE:
                 return 0
             if m.transmission_weight > 0 or m.subsurface_weight > 0:

@@ -1,5 +1,5 @@
 """The renderer's launch plan WITHOUT a GPU: plan_launches (crust-render_amd/csrc/crt_internal.h) decides once per batch
-which kernel instances run it; kernels/pathtrace.hip only looks the named instances up in its table and loops. Here the
+which kernel instances run it; kernels/pathtrace.hip only looks the named instances up in its table, render.cpp loops. Here the
 function is compiled as plain C++ (tests/launch_plan/plan_sweep.cpp, own main) and run as a child process.
 
 The property sweep: for every engine outcome select_engine gives over the scene grid (direct leaves, packets, LDS
