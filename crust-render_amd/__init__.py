@@ -190,6 +190,11 @@ ABI_SYMBOLS_GUIDING = [
     "crt_guiding_config_default", "crt_guiding_new", "crt_guiding_free", "crt_guiding_update", "crt_guiding_image",
     "crt_guiding_stats", "crt_guiding_sample_n", "crt_guiding_pdf_n", "crt_material_scatter_guided_n",
 ]
+# include/crt_face_textures.h: per-face colour textures (textures.py), declared beside crt.h for the same reason.
+ABI_SYMBOLS_FACE_TEXTURES = [
+    "crt_face_textures_new", "crt_face_textures_free", "crt_face_textures_image", "crt_face_resolve_n",
+    "crt_face_texture_eval_n", "crt_material_scatter_faces_n", "crt_material_eval_faces_n", "crt_renderer_set_face_textures",
+]
 
 _lib = None
 
@@ -336,6 +341,18 @@ def lib():
         L.crt_guiding_sample_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.crt_guiding_pdf_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.crt_material_scatter_guided_n.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "crt_face_textures_new"):  # per-face textures (textures.py; absent from older A/B variant libraries)
+        L.crt_face_textures_new.restype = vp
+        L.crt_face_textures_new.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+        L.crt_face_textures_free.restype = None
+        L.crt_face_textures_free.argtypes = [vp]
+        L.crt_face_textures_image.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.crt_face_resolve_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.crt_face_texture_eval_n.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, vp]
+        L.crt_material_scatter_faces_n.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp]
+        L.crt_material_eval_faces_n.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "crt_renderer_set_face_textures"):  # textured renders
+        L.crt_renderer_set_face_textures.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -872,6 +889,15 @@ class Renderer:
         _check(lib().crt_renderer_set_volumes(self.h, vol.h if vol is not None else None), "crt_renderer_set_volumes")
         self.volumes = vol
 
+    def set_face_textures(self, ft):
+        """Binds a per-face texture aggregate (textures.FaceTextures: its bindings keyed by this renderer's geom_ids, its
+        material_texture indexed like the renderer's material table) for the batches that follow, or detaches it (None):
+        textured surfaces in the wavefront renderer (crt_face_textures.h, crt_renderer_set_face_textures). The renderer
+        keeps the aggregate alive; the image is uploaded inside the call. A hit without a binding, a texture or a face
+        shades with the authored colour, to the bits of the unbound renderer."""
+        _check(lib().crt_renderer_set_face_textures(self.h, ft.h if ft is not None else None), "crt_renderer_set_face_textures")
+        self.face_textures = ft
+
     def render_samples_stats(self, sample_begin, sample_count, stream=None):
         st = (CrtTravStats * 2)()
         _check(lib().crt_render_samples_stats(self.h, sample_begin, sample_count, _stream_ptr(stream), st),
@@ -943,13 +969,14 @@ class Renderer:
         and traced the camera rays, and the first extend ran over the rays it deferred; camera_vertex: k_camera_vertex also
         shaded their first vertex, and the first extend and shade ran over the rays it deferred; pixel_table: that launch
         read each sample's per-pixel words from the table the renderer filled at creation; cull_root_lds: its root cull
-        read the root node from the launch's LDS window."""
+        read the root node from the launch's LDS window; face_textures: the batch was a textured render (set_face_textures:
+        the FACES extend and shade instances ran)."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
         return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
                     slim_state=bool(out[1] & 8), volumes=bool(out[1] & 16), camera_trace=bool(out[1] & 32),
                     camera_vertex=bool(out[1] & 64), pixel_table=bool(out[1] & 128), cull_root_lds=bool(out[1] & 256),
-                    grid=int(out[2]))
+                    face_textures=bool(out[1] & 512), grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""
@@ -1070,4 +1097,5 @@ from . import stats  # noqa: E402,F401  (RenderStats + the reference's report la
 from . import shading  # noqa: E402,F401  (Material / Light as batched device functions: the shading seam)
 from . import volumes  # noqa: E402,F401  (volume regions as batched device functions: fog and smoke behind the ABI)
 from . import guiding  # noqa: E402,F401  (the path guiding field as batched device functions: SD-tree sample, pdf, guided bounce)
+from . import textures  # noqa: E402,F401  (per-face colour textures as batched device functions: face maps, atlas, textured shading)
 from . import synthetic  # noqa: E402,F401  (scenes built in code: the labelled stand-in for BASELINE config 5)

@@ -382,7 +382,8 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
 // tests/test_launch_plan.py sweeps the function on the CPU.
 // ---------------------------------------------------------------------------------------------
 enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC,
-                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME, KF_EXTEND_DEFERRED, KF_CAMERA, KF_CAMERA_VERTEX };
+                               KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME, KF_EXTEND_DEFERRED, KF_CAMERA, KF_CAMERA_VERTEX,
+                               KF_EXTEND_FACES, KF_SHADE_FACES };
 struct InstanceKey {  // a kernel template and its arguments, in the template's order (bools as 0 / 1)
   uint8_t family = KF_NONE;
   uint8_t arg[5] = {0, 0, 0, 0, 0};
@@ -450,6 +451,23 @@ struct InstanceKey {  // a kernel template and its arguments, in the template's 
   X(SHADE_VOL, k_shade_vol, 0, 0, false) X(SHADE_VOL, k_shade_vol, 0, 0, true) X(SHADE_VOL, k_shade_vol, 0, 1, true) X(SHADE_VOL, k_shade_vol, 0, 2, true) \
   X(SHADE_VOL, k_shade_vol, 1, 0, false) X(SHADE_VOL, k_shade_vol, 1, 0, true) X(SHADE_VOL, k_shade_vol, 1, 1, true) X(SHADE_VOL, k_shade_vol, 1, 2, true) \
   X(SHADE_VOL, k_shade_vol, 2, 0, false) X(SHADE_VOL, k_shade_vol, 2, 0, true) X(SHADE_VOL, k_shade_vol, 2, 1, true) X(SHADE_VOL, k_shade_vol, 2, 2, true)
+// Textured renders (PlanInputs::faces, crt_renderer_set_face_textures). k_extend_faces<WIDE, COLD>: k_extend whose emit also
+// writes the hit's (prim_id, u, v) record — the engine width select_engine picked, the cold state that carries u, v
+// (kColdAll, with the curve arms where the image holds curves). k_shade_faces<MATS, INF, LIT>: the shade instances over
+// the MatFace view, instantiated like k_shade_vol's — three waves, raw material records. Lists of their own: a plan
+// names them in `extend` / `shade` with these families.
+#if CRT_WIDE_DIRECT_BUILD
+#define CRT_WIDE_DIRECT_INSTANCES_EXTEND_FACES(X) X(EXTEND_FACES, k_extend_faces, 2, 7)
+#else
+#define CRT_WIDE_DIRECT_INSTANCES_EXTEND_FACES(X)
+#endif
+#define CRT_INSTANCES_EXTEND_FACES(X) /* k_extend_faces<WIDE, COLD> */ \
+  X(EXTEND_FACES, k_extend_faces, 0, 7) X(EXTEND_FACES, k_extend_faces, 1, 7) CRT_WIDE_DIRECT_INSTANCES_EXTEND_FACES(X) \
+  X(EXTEND_FACES, k_extend_faces, 0, 23) X(EXTEND_FACES, k_extend_faces, 0, 55)
+#define CRT_INSTANCES_SHADE_FACES(X) /* k_shade_faces<MATS, INF, LIT> */ \
+  X(SHADE_FACES, k_shade_faces, 0, 0, false) X(SHADE_FACES, k_shade_faces, 0, 0, true) X(SHADE_FACES, k_shade_faces, 0, 1, true) X(SHADE_FACES, k_shade_faces, 0, 2, true) \
+  X(SHADE_FACES, k_shade_faces, 1, 0, false) X(SHADE_FACES, k_shade_faces, 1, 0, true) X(SHADE_FACES, k_shade_faces, 1, 1, true) X(SHADE_FACES, k_shade_faces, 1, 2, true) \
+  X(SHADE_FACES, k_shade_faces, 2, 0, false) X(SHADE_FACES, k_shade_faces, 2, 0, true) X(SHADE_FACES, k_shade_faces, 2, 1, true) X(SHADE_FACES, k_shade_faces, 2, 2, true)
 // The camera launches (LaunchPlan::camera_trace / camera_vertex): TABLE = the sample loop reads the per-pixel table,
 // ROOT_LDS = the cull reads the root from the LDS window, DRV = shade_early's table. Lists of their own: a plan names
 // the instance through camera_key().
@@ -495,6 +513,12 @@ struct PlanInputs {
   // k_volume between extend and shade, the VOL shade instances and — where the shadow stage runs — k_shadow_volume ahead
   // of k_shadow. false: exactly the plan of a renderer that never heard of volumes.
   bool volumes = false;
+  // A per-face texture aggregate is bound (crt_renderer_set_face_textures): one launch per stage whatever the batch size,
+  // the FACES extend instance (its emit keeps prim_id, u, v per hit) and the FACES shade instances (MatFace). No fused
+  // kernel and no tail, no camera-trace / camera-vertex / pixel-table launch, no pipelined or slim shade, no derived
+  // material table; material_texture is indexed by geom_id whether or not the material table is deduplicated.
+  // Not with volumes and not in the stats build: refused. false: exactly the plan of a renderer that never heard of it.
+  bool faces = false;
   // CRT_CAMERA_TRACE: 0 = generate and the first extend as before, 1 = k_camera wherever the result allows, 2 / 3 = the
   // same with every surviving ray deferred / with a one-entry stack (tests: the list and the deferred instance), -1 = the
   // host rule below
@@ -581,6 +605,8 @@ struct LaunchPlan {
   // of k_shadow where the shadow stage runs; `shade` then names a KF_SHADE_VOL instance. none = not launched.
   bool volumes = false;
   InstanceKey volume_key, shadow_volume_key;
+  // Textured renders (PlanInputs::faces): `extend` names a KF_EXTEND_FACES instance, `shade` a KF_SHADE_FACES one.
+  bool faces = false;
   // Camera rays traced where they are made (kernels/pathtrace.hip, k_camera): one launch generates, culls and traces the
   // batch's camera rays, one ray per lane, and writes their hit records; the first extend is the k_extend_deferred
   // instance over the few rays k_camera could not finish. `extend` names the same instance whatever this says.
@@ -644,17 +670,19 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
   // instances sit at their register limit, below; the walk is a kernel of its own between two stages).
   if (q.volumes) pl.fused = false;
   pl.volumes = q.volumes;
+  if (q.faces) pl.fused = false;  // textured renders likewise: the FACES instances are per-stage kernels
+  pl.faces = q.faces;
   const bool stage = !pl.fused, lit = q.n_lights > 0;
   pl.wide = stage && e.wide;  // the fused kernel is a three-wave kernel whatever the scene prefers
   // The TAIL: from bounce `tail_from` on, what is left of the batch — roulette has ended all but a few paths per ten
   // thousand by then (bench: 6.6 M of 531 M rays at bounce 4, 0.1 M at bounce 6) — runs as ONE launch of the fused
   // path-loop kernel over the same segments instead of two or three launches per bounce up to the depth limit (bench,
   // depth 32: 52 launches, ~2 ms of a 137 ms step). Not for the stats build: its kernels count.
-  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights && !q.volumes;
+  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights && !q.volumes && !q.faces;
   if (tail) pl.tail_at = (uint32_t)q.tail_from;
   // camera paths as 16-byte records: per-stage launches of an UNLIT scene, pinhole camera, static scene
   // (not in a volume render: k_volume reads and rewrites the full form)
-  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion && !q.volumes) ? 1u : 0u;
+  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion && !q.volumes && !q.faces) ? 1u : 0u;
   // The root cull (generate_segment_cull): per-stage launches of an image whose root is a node, when a camera ray that
   // escapes ends on the sky gradient — a depth limit above 0 and no light at infinity (their escaped rays take the
   // vertex step) — and where the frame shows enough background for it to pay (CRT_ROOT_CULL=1 skips that estimate). Not
@@ -700,6 +728,11 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
       pl.shade = key(KF_SHADE_VOL, q.mats_kind, q.has_env ? 2 : (q.has_inf_lights ? 1 : 0), lit);
       pl.volume_key = key(KF_VOLUME, 0);
       if (pl.shadow) pl.shadow_volume_key = key(KF_SHADOW_VOLUME, 0);
+    } else if (q.faces) {  // the FACES instances: the engine width as picked, the cold state with u, v; three-wave shade, raw records
+      const int faces_cold = e.curve ? curve_cold : (int)kColdAll;
+      pl.ext_cold = faces_cold;
+      pl.extend = key(KF_EXTEND_FACES, width, faces_cold);
+      pl.shade = key(KF_SHADE_FACES, q.mats_kind, q.has_env ? 2 : (q.has_inf_lights ? 1 : 0), lit);
     } else if (shade_wide && shade_pipe_fits(q) && q.noclassify_from > 0) pl.shade_early = key(KF_SHADE_PIPE, drv);
     pl.slim_state = pl.shade_piped() && q.no_emitter && q.slim_state != 0;
     if (pl.shadow) {
@@ -724,10 +757,12 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
     pl.cull_root_lds = pl.camera_trace && pl.root_cull && q.cull_root_lds_knob != 0 && q.scene.root == 0 && q.scene.n_nodes > 0;
   }
   const bool ok = !(q.volumes && q.stats) &&  // the stats build counts no walk: refused (crt_render_samples_stats)
+                  !(q.faces && (q.stats || q.volumes)) &&  // textured renders: no stats build, not beside volumes
+                  !(q.faces && pl.extend.arg[0] == 2 && !q.wide_direct_build) &&
                   (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
-                  (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.extend.arg[2])) &&
+                  (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.faces ? pl.extend.arg[1] : pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; pl.pixel_table = false; pl.cull_root_lds = false; }
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.faces = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; pl.pixel_table = false; pl.cull_root_lds = false; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }

@@ -32,6 +32,7 @@
 #include "../render_kernels.h"
 #include "camera_pixel.hip.h"
 #include "shade.hip.h"
+#include "faces.hip.h"
 #include "traverse_camera.hip.h"
 #include "traverse_pool.hip.h"
 #include "vertex_simple.hip.h"
@@ -667,10 +668,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_camera(Params P, PathSoA S, uint3
 // fetch has no registers for the branch — 13 -> 27, 33 -> 97, 52 -> 122 spilled registers in the lit k_path instances).
 // DEFER (k_extend_deferred): the rays are the camera rays k_camera left to this launch — their slot numbers come from the
 // segment's list (defer_list: the other state buffer's plane `a`), their count from Counters::cam_defer.
-template <bool STATS, int WIDE, int COLD, bool COMPACT, bool DEFER = false>
+// FACES (k_extend_faces): emit also keeps the hit's (prim_id, u, v, 0) in fplane, slot for slot beside H — what a
+// per-face texture's lookup needs of the kernel's hit (rt_world.rs:212-218); COLD then carries u, v.
+template <bool STATS, int WIDE, int COLD, bool COMPACT, bool DEFER = false, bool FACES = false>
 __device__ __forceinline__ void extend_segment(const Params &P, const PathSoA &S, const HitSoA &H, Counters *C, int cur,
                                                int first, CrtTravStats *tstats, uint32_t *engine_lds,
-                                               const uint32_t *defer_list = nullptr) {
+                                               const uint32_t *defer_list = nullptr, uint4 *fplane = nullptr) {
   __shared__ uint32_t pre[kBins + 1];
   bins_prefix(&C->seg[cur][blockIdx.x * kBins], pre);
   const uint32_t n = DEFER ? C->cam_defer[blockIdx.x] : pre[kBins];
@@ -703,6 +706,7 @@ __device__ __forceinline__ void extend_segment(const Params &P, const PathSoA &S
       const bool front = dot3(dx, dy, dz, h.nx, h.ny, h.nz) < 0.0f;  // scene.rs:356-359
       st_hit(&H.h[i], make_float4(h.t, front ? h.nx : -h.nx, front ? h.ny : -h.ny, front ? h.nz : -h.nz));
       st_hit(&H.geom[i], h.geom | (front ? 0x80000000u : 0u));
+      if (FACES) fplane[i] = make_uint4(h.prim, __float_as_uint(h.u), __float_as_uint(h.v), 0u);
     } else {
       st_hit(&H.geom[i], kInvalid);
     }
@@ -732,6 +736,42 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend_
   extend_segment<STATS, WIDE, COLD, true, true>(P, S, H, C, cur, first, tstats, engine_lds, defer_list);
 }
 
+// The extend of textured renders (LaunchPlan::faces): the engine instance the image runs, with the cold state that holds
+// u, v. A kernel of its own, so that k_extend is untouched.
+template <int WIDE, int COLD>
+__global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend_faces(Params P, PathSoA S, HitSoA H, Counters *C, int cur,
+                                                                           int first, CrtTravStats *tstats, uint4 *fplane) {
+  static_assert((COLD & (int)kColdUV) != 0, "the face lookup reads the hit's barycentrics");
+  __shared__ __attribute__((aligned(16))) uint32_t engine_lds[WIDE ? kEngineLdsWide : kEngineLdsDwords];
+  extend_segment<false, WIDE, COLD, true, false, true>(P, S, H, C, cur, first, tstats, engine_lds, nullptr, fplane);
+}
+
+// The view a vertex's scatter and evals run through. Unbound instances: the table's own view, the very object the vertex
+// code named before textures existed (view_of hands its reference back). FACES: a MatFace beside it — the record with
+// the texel of the hit's face in the place of base_color where the geometry has a face map, the material a texture and
+// the face resolves (openpbr.rs:1011-1024); every other lane carries the record's own colour, which gives the untextured
+// view's bits. Emission reads the table's view in either form: the authored colour, as upstream.
+template <bool FACES> struct FacesTag {};
+struct NoFaceView {};
+template <class MV>
+__device__ __forceinline__ NoFaceView face_view(FacesTag<false>, const MV &, const FaceView *, const uint4 *, uint32_t, uint32_t) { return NoFaceView{}; }
+template <class MV>
+__device__ __forceinline__ MatFace face_view(FacesTag<true>, const MV &mv, const FaceView *FV, const uint4 *fplane, uint32_t i, uint32_t geom) {
+  const CrtMaterial &m = mv.raw();
+  V3 base = ld3(m.base_color);
+  if (geom < FV->n_geoms && FV->geoms[geom] != kFaceNone) {  // the geometry has a binding: read the hit's record
+    const uint4 r = fplane[i];
+    const FaceCoord c = face_resolve(*FV, geom, r.x, __uint_as_float(r.y), __uint_as_float(r.z));
+    const uint32_t tex = geom < FV->n_materials ? FV->material_texture[geom] : kFaceNone;
+    if (tex != kFaceNone && c.face != kNoFace) base = face_texture_eval(*FV, tex, c.face, c.u, c.v);
+  }
+  return MatFace{m, BaseTexel{base}};
+}
+template <class MV>
+__device__ __forceinline__ const MV &view_of(const MV &mv, const NoFaceView &) { return mv; }
+template <class MV>
+__device__ __forceinline__ const MatFace &view_of(const MV &, const MatFace &fv) { return fv; }
+
 // ---- shade: one iteration of trace_path's loop body for every live path (tracer.rs:1118-1530) ----
 // LIT: the light list is not empty. Unlit scenes (cornellbox, the bench scene: sky only) run an instance without the
 // light-sampling block, its second BSDF evaluation, the emitter MIS weights and the previous-vertex plane — code they
@@ -753,13 +793,14 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : CRT_EXTEND_WAVES) void k_extend_
 // behind a kVolScatter hit word — its values are loaded into the variables of the tail below, which compacts, queues the
 // shadow request and stages as for any vertex; the vertex code is skipped. Every shadow request's K_NEE_SHADOW seed goes
 // to qseed (k_shadow_volume walks the segment with it).
-template <int MATS, int INF, bool LIT, int ARENA, bool DRV, bool VOL = false>
+template <int MATS, int INF, bool LIT, int ARENA, bool DRV, bool VOL = false, bool FACES = false>
 __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                               const ShadowSoA &Q, Counters *C, int cur, float4 *staging,
                                               uint32_t *sobol_tab /* ARENA dwords: Sobol tables, then the material table */,
                                               bool first /* camera paths whose plane c was not written (generate_segment) */,
                                               bool all_pending = false /* no CLASSIFY pass: every path takes the vertex step */,
-                                              uint32_t *qseed = nullptr /* VOL: one word per shadow-queue slot */) {
+                                              uint32_t *qseed = nullptr /* VOL: one word per shadow-queue slot */,
+                                              const FaceView *FV = nullptr, const uint4 *fplane = nullptr /* FACES */) {
   constexpr bool MEDIA = MATS == 2, SIMPLE = MATS == 0;
   static_assert(SIMPLE || !DRV, "the derived record covers what a simple-material table reads (shade.hip.h)");
   typedef MatTable<DRV> Table;
@@ -1087,6 +1128,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
           L = L + beta * background;
         } else {
           const auto mat = Table::view(mats, P, mat_i);
+          const auto fmat = face_view(FacesTag<FACES>{}, mat, FV, fplane, i, geom);
           // tracer.rs:1352-1361: a scattering medium already paid e^{-sigma_bar t} through the free-flight
           // competition, only the chromatic correction remains; a clear one keeps pure Beer-Lambert.
           V3 atten = splat(1.0f);
@@ -1118,7 +1160,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
               const float light_pdf = rmax(ls.pdf / (float)n_lights, 1e-6f);
               V3 brdf_value; float brdf_pdf;
               V3 nee = splat(0.0f);
-              if (mat_eval<SIMPLE>(mat, rd, rec, ls.direction, brdf_value, brdf_pdf)) {
+              if (mat_eval<SIMPLE>(view_of(mat, fmat), rd, rec, ls.direction, brdf_value, brdf_pdf)) {
                 const float weight = light_weight(P.strategy, light_pdf, brdf_pdf);
                 V3 c = (ls.radiance * brdf_value) * cosine;
                 c = c * splat(1.0f);  // shadow_tr == ONE when unoccluded
@@ -1131,7 +1173,7 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
 
           // === 2. indirect lighting by BSDF sampling (tracer.rs:1459-1523) ===
           Scatter sample;
-          if (mat_scatter<SIMPLE>(mat, rd, rec, new_domain(vdom, K_BSDF), sample, sobol_tab)) {
+          if (mat_scatter<SIMPLE>(view_of(mat, fmat), rd, rec, new_domain(vdom, K_BSDF), sample, sobol_tab)) {
             const V3 dir = normalize(sample.dir);
             const float cosine = sample.delta ? 1.0f : fabs_(dot(rec.normal, dir));
             const V3 factor = (sample.value * cosine) / sample.pdf;
@@ -1240,6 +1282,17 @@ __global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_vol(Params P,
   static_assert(LIT || !INF, "lights at infinity are lights");
   __shared__ uint32_t sobol_tab[kArenaDwords];
   shade_segment<MATS, INF, LIT, kArenaDwords, false, true>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0, qseed);
+}
+
+// The instances of textured renders (LaunchPlan::faces), instantiated as k_shade_vol's: three waves, raw material records.
+template <int MATS, int INF, bool LIT>
+__global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_faces(Params P, PathSoA S, PathSoA N, HitSoA H, ShadowSoA Q,
+                                                                         Counters *C, int cur, float4 *staging, int first, FaceView F,
+                                                                         const uint4 *fplane) {
+  static_assert(LIT || !INF, "lights at infinity are lights");
+  __shared__ uint32_t sobol_tab[kArenaDwords];
+  shade_segment<MATS, INF, LIT, kArenaDwords, false, false, true>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0,
+                                                                  nullptr, &F, fplane);
 }
 
 // ---- volume: the regions a segment crosses (volume.hip.h), between extend and shade of a volume render ----
@@ -2075,6 +2128,8 @@ static const InstanceRow<ShadeFn> kShadeRows[] = {CRT_INSTANCES_SHADE(CRT_ROW)};
 static const InstanceRow<ShadePipeFn> kShadePipeRows[] = {CRT_INSTANCES_SHADE_PIPE(CRT_ROW) CRT_INSTANCES_SHADE_PIPE_SLIM(CRT_ROW)};
 static const InstanceRow<ShadowFn> kShadowRows[] = {CRT_INSTANCES_SHADOW(CRT_ROW)};
 static const InstanceRow<ShadeVolFn> kShadeVolRows[] = {CRT_INSTANCES_SHADE_VOL(CRT_ROW)};
+static const InstanceRow<ExtendFacesFn> kExtendFacesRows[] = {CRT_INSTANCES_EXTEND_FACES(CRT_ROW)};
+static const InstanceRow<ShadeFacesFn> kShadeFacesRows[] = {CRT_INSTANCES_SHADE_FACES(CRT_ROW)};
 static const InstanceRow<CameraFn> kCameraRows[] = {CRT_INSTANCES_CAMERA(CRT_ROW)};
 static const InstanceRow<CameraVertexFn> kCameraVertexRows[] = {CRT_INSTANCES_CAMERA_VERTEX(CRT_ROW)};
 #undef CRT_ROW
@@ -2093,6 +2148,13 @@ int resolve_kernels(const LaunchPlan &plan, BatchKernels &k) {
   k = BatchKernels{};
   if (plan.volumes && !find_instance(kShadeVolRows, plan.shade, k.shade_vol)) return CRT_ERR_UNSUPPORTED;
   if (plan.volumes && (plan.volume_key.none() || plan.fused)) return CRT_ERR_UNSUPPORTED;
+  if (plan.faces) {  // textured renders: the two FACES instances in the place of extend and shade, per stage, nothing else new
+    if (plan.volumes || plan.fused || plan.camera_trace || plan.shade_piped() || !plan.path.none()) return CRT_ERR_UNSUPPORTED;
+    if (!find_instance(kExtendFacesRows, plan.extend, k.extend_faces) || !find_instance(kShadeFacesRows, plan.shade, k.shade_faces) ||
+        !find_instance(kShadowRows, plan.shadow_key, k.shadow) || !k.extend_faces || !k.shade_faces)
+      return CRT_ERR_UNSUPPORTED;
+    return CRT_OK;
+  }
   const InstanceKey camera = plan.camera_key();
   if (!find_instance(kPathRows, plan.path, k.path) || !find_instance(kExtendRows, plan.extend, k.extend) ||
       (!plan.volumes && !find_instance(kShadeRows, plan.shade, k.shade)) || !find_instance(kShadePipeRows, plan.shade_early, k.shade_pipe) ||

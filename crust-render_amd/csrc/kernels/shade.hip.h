@@ -256,13 +256,16 @@ __device__ __forceinline__ V3 thin_film_fresnel_metal(float cos1, float eta1, fl
 struct LobePmf { float p_diffuse, p_specular, p_coat, p_fuzz, p_transmission; };
 __device__ __forceinline__ float luma(V3 c) { return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z; }
 
-__device__ __forceinline__ LobePmf lobe_pmf(const CrtMaterial &m) {  // openpbr.rs:317-378
+// BASE answers get(m): the authored base colour, read where the reference reads it, or the texel a per-face texture put in
+// its place (openpbr.rs:1011-1024: before the pmf is built) — BaseAuthored / BaseTexel below.
+template <class BASE>
+__device__ __forceinline__ LobePmf lobe_pmf(const CrtMaterial &m, const BASE &base) {  // openpbr.rs:317-378
   const float f0_diel = f0_from_ior(m.specular_ior);
   const float f0_coat = f0_from_ior(m.coat_ior);
-  const float base_luma = rmax(luma(ld3(m.base_color)), 0.02f);
+  const float base_luma = rmax(luma(base.get(m)), 0.02f);
   const float spec_luma = rmax(luma(ld3(m.specular_color)), 0.02f);
   const float fuzz_luma = rmax(luma(ld3(m.fuzz_color)), 0.02f);
-  const float w_metal = m.base_metalness * m.specular_weight * rmax(luma(ld3(m.base_color) * m.base_weight), 0.02f);
+  const float w_metal = m.base_metalness * m.specular_weight * rmax(luma(base.get(m) * m.base_weight), 0.02f);
   const float w_diel_spec = (1.0f - m.base_metalness) * m.specular_weight * spec_luma * f0_diel;
   const float w_specular = rmax(w_metal + w_diel_spec, 1e-4f);
   const float w_diffuse = rmax((1.0f - m.base_metalness) * (1.0f - m.transmission_weight) * m.base_weight * base_luma *
@@ -295,7 +298,10 @@ __device__ __forceinline__ int lobe_pick(const LobePmf &p, float u) {  // openpb
 //               points (shade_seam.hip), the general kernel instances and CRT_MAT_DERIVED=0 run;
 //   MatDerived  reads it from a DevMaterial record that derive_material() filled once per renderer THROUGH MatRaw, so no
 //               formula exists twice and every stored value has the bits the vertex would have computed
-//               (-ffp-contract=off: one IEEE operation gives one result wherever it runs).
+//               (-ffp-contract=off: one IEEE operation gives one result wherever it runs);
+//   MatFace     is MatRaw with the base colour held in three registers: the texel of a per-face texture in the place
+//               of the record's base_color (kernels/faces.hip.h), at every site scatter and eval read it — the lobe pmf,
+//               the diffuse albedo, the metal F0 and the coat darkening. Emission keeps the authored colour, as upstream.
 // Only whole material-only sub-expressions are stored; `x / d` with a per-vertex x stays a division by the stored d.
 // DevMaterial covers what a hit on a SIMPLE table reads; the arms SIMPLE compiles out (coat, fuzz, thin film, rough
 // transmission) and the thin pass-through arm keep reading the raw record through raw(). The record has the size of a
@@ -316,14 +322,24 @@ struct DevMaterial {
 };
 static_assert(sizeof(DevMaterial) == sizeof(CrtMaterial), "either table is staged under the same LDS budget");
 
-struct MatRaw {
+struct BaseAuthored {
+  __device__ __forceinline__ V3 get(const CrtMaterial &m) const { return ld3(m.base_color); }
+};
+struct BaseTexel {
+  V3 c;
+  __device__ __forceinline__ V3 get(const CrtMaterial &) const { return c; }
+};
+template <class BASE>
+struct MatRawOf {
   const CrtMaterial &m;
+  BASE base;
   __device__ __forceinline__ const CrtMaterial &raw() const { return m; }
   __device__ __forceinline__ uint32_t kind() const { return m.kind; }
   __device__ __forceinline__ V3 emission() const {
     return m.kind == CRT_MAT_EMISSIVE ? ld3(m.emission_color) : ld3(m.emission_color) * m.emission_luminance;
   }
-  __device__ __forceinline__ LobePmf pmf() const { return lobe_pmf(m); }
+  __device__ __forceinline__ V3 base_color() const { return base.get(m); }
+  __device__ __forceinline__ LobePmf pmf() const { return lobe_pmf(m, base); }
   __device__ __forceinline__ Alpha spec_alpha() const { return alpha_of(m.specular_roughness, m.specular_roughness_anisotropy); }
   __device__ __forceinline__ Alpha coat_alpha() const { return alpha_of(m.coat_roughness, m.coat_roughness_anisotropy); }
   __device__ __forceinline__ float f0_diel() const { return f0_from_ior(m.specular_ior); }
@@ -332,7 +348,7 @@ struct MatRaw {
     return m.base_weight * (1.0f - m.base_metalness) * (1.0f - m.transmission_weight);
   }
   __device__ __forceinline__ EonConst eon() const {
-    const V3 diffuse_color = lerp(ld3(m.base_color), ld3(m.subsurface_color), m.subsurface_weight);
+    const V3 diffuse_color = lerp(base_color(), ld3(m.subsurface_color), m.subsurface_weight);
     const V3 rho = diffuse_color * presence();
     return eon_const(rho, m.base_diffuse_roughness);
   }
@@ -340,15 +356,18 @@ struct MatRaw {
   __device__ __forceinline__ float one_m_metalness() const { return 1.0f - m.base_metalness; }
   __device__ __forceinline__ float specular_weight() const { return m.specular_weight; }
   __device__ __forceinline__ V3 f0_diel_base() const { return ld3(m.specular_color) * f0_diel() * m.specular_weight; }
-  __device__ __forceinline__ V3 metal_f0() const { return ld3(m.base_color) * m.base_weight; }
+  __device__ __forceinline__ V3 metal_f0() const { return base_color() * m.base_weight; }
   __device__ __forceinline__ V3 f82_a() const { return f82_tint_a(metal_f0(), ld3(m.specular_color)); }
   __device__ __forceinline__ float base_atten() const { return rclamp(1.0f - m.fuzz_weight, 0.0f, 1.0f); }
 };
+using MatRaw = MatRawOf<BaseAuthored>;  // MatRaw{m}
+using MatFace = MatRawOf<BaseTexel>;    // MatFace{m, {texel}}
 struct MatDerived {
   const DevMaterial &d;
   const CrtMaterial &r;  // the record d was derived from: only the arms named above read it
   __device__ __forceinline__ const CrtMaterial &raw() const { return r; }
   __device__ __forceinline__ uint32_t kind() const { return d.kind; }
+  __device__ __forceinline__ V3 base_color() const { return ld3(r.base_color); }
   __device__ __forceinline__ V3 emission() const { return ld3(d.emission); }
   __device__ __forceinline__ LobePmf pmf() const { return LobePmf{d.pmf[0], d.pmf[1], d.pmf[2], d.pmf[3], d.pmf[4]}; }
   __device__ __forceinline__ Alpha spec_alpha() const { return Alpha{d.spec_alpha[0], d.spec_alpha[1], d.spec_alpha[2]}; }
@@ -473,10 +492,11 @@ __device__ __forceinline__ V3 coat_passage(const CrtMaterial &m, float cos_theta
   const float f_coat = fresnel_schlick_scalar(cos_i, f0_from_ior(m.coat_ior));
   return absorb * (1.0f - m.coat_weight * f_coat);
 }
-template <bool SIMPLE>
-__device__ __forceinline__ V3 coat_attenuation(const CrtMaterial &m, float cos_v, float cos_l) {
+template <bool SIMPLE, class MV>
+__device__ __forceinline__ V3 coat_attenuation(const MV &mv, float cos_v, float cos_l) {
+  const CrtMaterial &m = mv.raw();
   if (SIMPLE || m.coat_weight <= 0.0f) return splat(1.0f);
-  const V3 dark = coat_darkening_factor(ld3(m.base_color), m.coat_ior, m.coat_darkening);
+  const V3 dark = coat_darkening_factor(mv.base_color(), m.coat_ior, m.coat_darkening);
   return coat_passage(m, cos_v) * coat_passage(m, cos_l) * dark;
 }
 __device__ __forceinline__ V3 eval_fuzz(const CrtMaterial &m, V3 v_local, V3 l_local, V3 h_local) {
@@ -574,7 +594,7 @@ __device__ __forceinline__ V3 eval_all(const MV &mv, V3 v_local, V3 l_local, boo
   V3 coat = splat(0.0f);
   if (!SIMPLE && m.coat_weight > 0.0f) coat = eval_coat(m, v_local, l_local, h_local, mv.coat_alpha());
   const V3 fuzz = (!SIMPLE && m.fuzz_weight > 0.0f) ? eval_fuzz(m, v_local, l_local, h_local) : splat(0.0f);
-  const V3 coat_atten = coat_attenuation<SIMPLE>(m, v_local.z, l_local.z);
+  const V3 coat_atten = coat_attenuation<SIMPLE>(mv, v_local.z, l_local.z);
   return fuzz + (coat + coat_atten * (diffuse + specular)) * mv.base_atten();
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "render_kernels.h"
+#include "face_textures_internal.h"
 
 namespace crt {
 
@@ -35,6 +36,7 @@ struct Renderer {
     PathSoA S[2]{};
     HitSoA H{};
     ShadowSoA Q{};
+    uint4 *fplane = nullptr;       // textured renders: the hit's (prim_id, u, v, 0) record, slot for slot beside H
     uint32_t *qseed = nullptr;     // volume renders of lit scenes: the K_NEE_SHADOW seed of every shadow-queue slot
     Counters *C = nullptr;
     float4 *staging = nullptr;
@@ -69,6 +71,11 @@ struct Renderer {
   // kernels take it. nullptr: none — every batch then runs what it ran before volumes existed.
   CrtVolumes *volumes = nullptr;
   VolArgs vol{nullptr, nullptr, 0};
+  // The bound per-face texture aggregate (crt_renderer_set_face_textures): a reference of the renderer's own, and its device
+  // tables as the kernels take them. nullptr: none — every batch then runs what it ran before textures existed.
+  CrtFaceTextures *faces = nullptr;
+  dev::FaceView face_view{};
+  uint32_t n_materials_given = 0;  // the caller's table at creation, before any deduplication: what material bindings index
   // What the root cull can save grows with the share of the frame that shows background; what it costs does not:
   // generate's slab tests and compaction, plane d beside the compact form. So the renderer looks first: the root step of
   // the pixel-centre rays of a 32 x 18 grid over the frame, through the lens centre, on the host (at creation), and
@@ -117,6 +124,7 @@ struct Renderer {
       if (B.done) (void)hipEventDestroy(B.done);
     }
     if (ev_start) (void)hipEventDestroy(ev_start);
+    face_textures_release(faces);
     volumes_release(volumes);  // behind the synchronised lanes; the caller's stream is the caller's to drain (as for the scene)
     if (film) (void)hipFree(film);
     if (d_materials) (void)hipFree(d_materials);
@@ -178,9 +186,10 @@ struct Renderer {
     const size_t p16 = (cap * 16 + 255) & ~size_t(255);
     const size_t b16 = (bcap * 16 + 255) & ~size_t(255), b4 = (bcap * 4 + 255) & ~size_t(255);
     const bool lit = P.n_lights > 0, motion = P.has_motion != 0;
+    const size_t f16 = faces ? b16 : 0;  // the hit's face record plane (set_face_textures frees the blobs)
     const size_t p4 = (lit && volumes) ? ((cap * 4 + 255) & ~size_t(255)) : 0;  // the shadow queue's seed plane (set_volumes frees the blobs)
     // 2 x (a b c d [e] [16 B] + [time 4 B]) + hit (16 + 4) + shadow 3 x 16 [+ 4] + staging 16
-    blob_bytes = 2 * ((lit ? 5 : 4) * b16 + (motion ? b4 : 0)) + (b16 + b4) + (lit ? 3 * p16 : 0) + p4 + p16;
+    blob_bytes = 2 * ((lit ? 5 : 4) * b16 + (motion ? b4 : 0)) + (b16 + b4) + f16 + (lit ? 3 * p16 : 0) + p4 + p16;
     // CRT_MAX_BATCH_SLOTS (tests): a batch of more slots asks for more memory than any device has, so the allocation
     // fails the way it does on a part with too little free HBM (bench.py halves the batch then).
     const size_t want_bytes = (max_batch_slots && slots > max_batch_slots) ? ((size_t)1 << 46) : blob_bytes;
@@ -200,6 +209,7 @@ struct Renderer {
       S[b].time = motion ? (float *)take(b4) : nullptr;
     }
     H.h = (float4 *)take(b16); H.geom = (uint32_t *)take(b4);
+    B.fplane = f16 ? (uint4 *)take(f16) : nullptr;
     if (lit) { Q.a = (float4 *)take(p16); Q.b = (float4 *)take(p16); Q.c = (float4 *)take(p16); }
     B.qseed = p4 ? (uint32_t *)take(p4) : nullptr;
     staging = (float4 *)take(p16);
@@ -296,6 +306,7 @@ struct Renderer {
     in.mat_index = P.mat_index != nullptr; in.partition = P.partition; in.n_materials = P.n_materials; in.max_depth = P.max_depth;
     in.class_stats = P.class_stats;
     in.volumes = volumes != nullptr;
+    in.faces = faces != nullptr;
   }
   // The per-pixel camera table (kernels/camera_pixel.hip.h), at creation: built where the plan of a large batch of this
   // renderer names it — asked of plan_launches itself, so the rule stays in one place. No memory for it (32 bytes per
@@ -333,6 +344,10 @@ struct Renderer {
       set_error_text("render refused: the stats build does not run volume renders");
       return CRT_ERR_UNSUPPORTED;
     }
+    if (in.faces && (stats || in.volumes)) {
+      set_error_text("render refused: textured renders run neither the stats build nor beside volumes");
+      return CRT_ERR_UNSUPPORTED;
+    }
     if (plan_launches(in, last_plan) != CRT_OK) {
       set_error_text("render refused: the selected kernels (wide %d, cold %d / %d) cannot run this image (direct words %u, cold %u)",
                      (int)last_plan.wide, last_plan.ext_cold, last_plan.path_cold, P.scene.direct_leaves, P.scene.cold);
@@ -365,6 +380,7 @@ struct Renderer {
     if (const int rc = plan_lane(B, p, n_samples, d_tstats != nullptr)) return rc;
     const LaunchPlan plan = last_plan;
     if (plan.volumes != (volumes != nullptr)) return CRT_ERR_UNSUPPORTED;
+    if (plan.faces != (faces != nullptr) || (plan.faces && !B.fplane)) return CRT_ERR_UNSUPPORTED;
     BatchKernels k;
     if (const int rc = resolve_kernels(plan, k)) return rc;
     float4 *staging = B.staging;
@@ -419,9 +435,13 @@ struct Renderer {
         timed(0, st, [&] { hipLaunchKernelGGL(k.extend, dim3(grid), dim3(kBlock), 0, st, p0, S[cur], H, C, cur, first, d_tstats); });
       else if (first && plan.camera_trace)
         timed(0, st, [&] { hipLaunchKernelGGL(k.extend_deferred, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats, reinterpret_cast<const uint32_t *>(S[1 - cur].a)); });
+      else if (plan.faces)  // the FACES instance: the hit's (prim_id, u, v) kept beside the record
+        timed(0, st, [&] { hipLaunchKernelGGL(k.extend_faces, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats, B.fplane); });
       else
         timed(0, st, [&] { hipLaunchKernelGGL(k.extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
-      if (plan.volumes) {  // the walk, then the VOL shade instance (plane c is k_volume's to write: never `first`), then the shadow segments' walk
+      if (plan.faces) {  // the FACES shade instance (MatFace)
+        timed(1, st, [&] { hipLaunchKernelGGL(k.shade_faces, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, first | ((int)it >= plan.noclassify_from ? 2 : 0), face_view, (const uint4 *)B.fplane); });
+      } else if (plan.volumes) {  // the walk, then the VOL shade instance (plane c is k_volume's to write: never `first`), then the shadow segments' walk
         timed(3, st, [&] { hipLaunchKernelGGL(kStageKernels.volume, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, vol); });
         timed(1, st, [&] { hipLaunchKernelGGL(k.shade_vol, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (int)it >= plan.noclassify_from ? 2 : 0, B.qseed); });
         if (!plan.shadow_volume_key.none())
@@ -505,6 +525,7 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   P.scene = scene->p->dev->view;
   P.n_lights = (uint32_t)n_lights;
   P.n_materials = (uint32_t)n_materials;
+  r.n_materials_given = (uint32_t)n_materials;
   P.has_inf_lights = 0;
   for (size_t k = 0; k < n_lights; k++) {
     if (lights[k].kind > CRT_LIGHT_DOME_MAP) { set_error_text("crt_renderer_new: light %zu has the unknown kind %u", k, lights[k].kind); return nullptr; }
@@ -715,6 +736,10 @@ static int renderer_set_volumes(CrtRenderer *r, CrtVolumes *v) {
     set_error_text("crt_renderer_set_volumes: a CRT_REGEN_FIRST build holds no volume stage");
     return CRT_ERR_UNSUPPORTED;
   }
+  if (v && R.faces) {
+    set_error_text("crt_renderer_set_volumes: a per-face texture aggregate is bound; textures together with volumes are not built");
+    return CRT_ERR_UNSUPPORTED;
+  }
   VolumesView view;
   if (v) {  // the image is uploaded here, not by the first batch
     const int rc = volumes_device(v, view);
@@ -726,7 +751,7 @@ static int renderer_set_volumes(CrtRenderer *r, CrtVolumes *v) {
   for (Renderer::Lane &B : R.lanes) {
     if (B.stream) (void)hipStreamSynchronize(B.stream);
     if (B.blob) (void)hipFree(B.blob);
-    B.blob = nullptr; B.cap_slots = 0; B.blob_bytes = 0; B.qseed = nullptr;
+    B.blob = nullptr; B.cap_slots = 0; B.blob_bytes = 0; B.qseed = nullptr; B.fplane = nullptr;
   }
   volumes_retain(v);
   volumes_release(R.volumes);
@@ -738,9 +763,53 @@ int crt_renderer_set_volumes(CrtRenderer *r, CrtVolumes *v) {
   if (!r) return CRT_ERR_BAD_ARG;
   return abi_guard("crt_renderer_set_volumes", [&] { return renderer_set_volumes(r, v); });  // nothing unwinds through the ABI
 }
+// The FACES instances read plane d of camera paths like every shade instance; a CRT_REGEN_FIRST build has shade work
+// camera paths out again in instances of its own, which hold no FACES form: that A/B build renders no textures.
+static int renderer_set_face_textures(CrtRenderer *r, CrtFaceTextures *ft) {
+  Renderer &R = r->r;
+  if (ft == R.faces) return CRT_OK;
+  if (ft && kKernelBuild.regen_first) {
+    set_error_text("crt_renderer_set_face_textures: a CRT_REGEN_FIRST build holds no textured shade instances");
+    return CRT_ERR_UNSUPPORTED;
+  }
+  if (ft && R.volumes) {
+    set_error_text("crt_renderer_set_face_textures: a volume aggregate is bound; textures together with volumes are not built");
+    return CRT_ERR_UNSUPPORTED;
+  }
+  dev::FaceView view{};
+  if (ft) {
+    uint32_t n_geoms = 0, n_materials = 0;
+    face_textures_counts(ft, n_geoms, n_materials);
+    if (n_geoms > R.scene->n_geoms || n_materials > R.n_materials_given) {
+      set_error_text("crt_renderer_set_face_textures: the aggregate binds geometries below %u and materials below %u; the renderer has %u and %u",
+                     n_geoms, n_materials, R.scene->n_geoms, R.n_materials_given);
+      return CRT_ERR_BAD_ARG;
+    }
+    const int rc = face_textures_device(ft, view);  // the image is uploaded here, not by the first batch
+    if (rc != CRT_OK) return rc;
+  }
+  // nothing of an earlier batch may be in flight when the buffers change shape (the face record plane comes and goes with
+  // the binding) or the old aggregate's last reference goes
+  if (!CRT_HIP_OK(hipStreamSynchronize(R.last_stream))) return CRT_ERR_NO_DEVICE;
+  for (Renderer::Lane &B : R.lanes) {
+    if (B.stream) (void)hipStreamSynchronize(B.stream);
+    if (B.blob) (void)hipFree(B.blob);
+    B.blob = nullptr; B.cap_slots = 0; B.blob_bytes = 0; B.qseed = nullptr; B.fplane = nullptr;
+  }
+  face_textures_retain(ft);
+  face_textures_release(R.faces);
+  R.faces = ft;
+  R.face_view = view;
+  return CRT_OK;
+}
+int crt_renderer_set_face_textures(CrtRenderer *r, CrtFaceTextures *ft) {
+  if (!r) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_renderer_set_face_textures", [&] { return renderer_set_face_textures(r, ft); });  // nothing unwinds through the ABI
+}
 int crt_render_samples_stats(CrtRenderer *r, uint32_t sample_begin, uint32_t sample_count, void *stream,
                              CrtTravStats host_stats[2]) {
   if (!r || !host_stats) return CRT_ERR_BAD_ARG;
+  if (r->r.faces) { set_error_text("crt_render_samples_stats: the stats build does not run textured renders"); return CRT_ERR_UNSUPPORTED; }
   if (r->r.volumes) { set_error_text("crt_render_samples_stats: the stats build does not run volume renders"); return CRT_ERR_UNSUPPORTED; }
   CrtTravStats *d = nullptr;
   if (!CRT_HIP_OK(hipMalloc(&d, 2 * sizeof(CrtTravStats)))) return CRT_ERR_NO_DEVICE;
@@ -845,7 +914,7 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   out[0] = plan.fused ? 1u : 0u;
   out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u) |
            (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u) | (plan.camera_vertex ? 64u : 0u) |
-           (plan.pixel_table ? 128u : 0u) | (plan.cull_root_lds ? 256u : 0u);
+           (plan.pixel_table ? 128u : 0u) | (plan.cull_root_lds ? 256u : 0u) | (plan.faces ? 512u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "crt_internal.h"
+#include "kernels/faces.hip.h"  // dev::FaceView, passed by value to the FACES shade instances
 
 namespace crt {
 
@@ -155,6 +156,10 @@ using CameraVertexFn = void (*)(Params, PathSoA, PathSoA, Counters *, uint32_t, 
 using CameraFn = void (*)(Params, PathSoA, uint32_t *, HitSoA, Counters *, uint32_t, uint32_t, float4 *, uint32_t, const dev::PixelRec *);
 using ShadowFn = void (*)(Params, PathSoA, ShadowSoA, Counters *, float4 *, CrtTravStats *);
 using ShadeVolFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, uint32_t *);
+// Textured renders: the hit's (prim_id, u, v, 0) record plane beside HitSoA — an argument of its own, so that no other
+// kernel's arguments change — and the aggregate's tables (kernels/faces.hip.h).
+using ExtendFacesFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, CrtTravStats *, uint4 *);
+using ShadeFacesFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, dev::FaceView, const uint4 *);
 
 using GenerateFn = void (*)(Params, PathSoA, Counters *, uint32_t, uint32_t, float4 *);
 using VolumeFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, VolArgs);
@@ -193,6 +198,8 @@ struct BatchKernels {
   ShadeFn shade;
   ShadePipeFn shade_pipe, shade_slim;
   ShadeVolFn shade_vol;
+  ExtendFacesFn extend_faces;     // textured renders (LaunchPlan::faces): these two in the place of extend / shade
+  ShadeFacesFn shade_faces;
   ShadowFn shadow;
   CameraFn camera;                // the camera launch: one of the two, or neither (k_generate)
   CameraVertexFn camera_vertex;

@@ -389,9 +389,11 @@ class SceneDesc:
         self.volumes = []    # region dicts (volumes.region): only load(..., volumes=True) fills it; build_world ignores it
 
 
-def _triangulate(counts, indices, n_verts):  # usd_import.rs:1164-1214
-    tris, off = [], 0
-    for fc in counts:
+def _triangulate(counts, indices, n_verts, want_faces=False):  # usd_import.rs:1164-1214
+    """want_faces: also the face table (faces uint32, slices uint8: textures.FAN_*), index-parallel with the triangles; a
+    skipped face or triangle does not shift the ids of the faces after it."""
+    tris, faces, slices, off = [], [], [], 0
+    for face, fc in enumerate(counts):
         if fc < 3 or off + fc > len(indices):
             off += fc
             continue
@@ -400,11 +402,70 @@ def _triangulate(counts, indices, n_verts):  # usd_import.rs:1164-1214
             if min(i0, i1, i2) < 0 or max(i0, i1, i2) >= n_verts:
                 continue
             tris.append((i0, i1, i2))
+            faces.append(face)
+            slices.append(0 if fc == 3 else ((1 if k == 1 else 2) if fc == 4 else 3))  # Triangle, QuadLower / Upper, Unmappable
         off += fc
-    return np.asarray(tris, dtype=np.uint32).reshape(-1, 3)
+    tris = np.asarray(tris, dtype=np.uint32).reshape(-1, 3)
+    if want_faces:
+        return tris, np.asarray(faces, dtype=np.uint32), np.asarray(slices, dtype=np.uint8)
+    return tris
 
 
-def _material_of(prim, by_path):
+def _material_face_texture(mat, tex_ctx):
+    """material_ptex (usd_import.rs:2814-2841): the texture inputs:surfaceMap names, as an index into
+    desc.face_textures, or None. The loader is asked once per resolved path; a negative answer is cached too."""
+    value = mat.attr("inputs:surfaceMap")
+    if not isinstance(value, str) or not value:
+        return None
+    import os
+    path = value if os.path.isabs(value) else os.path.normpath(os.path.join(tex_ctx["dir"], value))
+    cache = tex_ctx["cache"]
+    if path not in cache:
+        tex = tex_ctx["loader"](path)
+        if tex is None:
+            cache[path] = None
+        else:
+            cache[path] = len(tex_ctx["textures"])
+            tex_ctx["textures"].append(tex)
+    return cache[path]
+
+
+def _disney_material(mat, target, tex_ctx):
+    """disney_to_openpbr (usd_import.rs:2745-2806): OpenPBR::default() with the PxrDisneyBsdf inputs the Material prim's
+    interface authors mapped onto it. baseColor is display-encoded: max(0)^2.2 (srgb_to_linear, :2882). sheen is not
+    mapped: Disney's sheen is added at grazing angles, OpenPBR's fuzz is mixed over everything beneath it."""
+    out = {"_path": target}
+    c = mat.attr("inputs:baseColor")
+    if c is not None:
+        out["base_color"] = tuple(float(np.power(np.maximum(f32(x), f32(0.0)), f32(2.2), dtype=np.float32)) for x in c)
+    for usd_name, field in (("metallic", "base_metalness"), ("roughness", "specular_roughness"), ("ior", "specular_ior"),
+                            ("anisotropic", "specular_roughness_anisotropy"), ("clearcoat", "coat_weight")):
+        v = mat.attr("inputs:" + usd_name)
+        if v is not None:
+            out[field] = float(v)
+    v = mat.attr("inputs:clearcoatGloss")
+    if v is not None:  # gloss is the complement of roughness
+        out["coat_roughness"] = float(min(max(f32(1.0) - f32(v), f32(0.0)), f32(1.0)))
+    v = mat.attr("inputs:specularTransmission")
+    if v is None:
+        v = mat.attr("inputs:refractionGain")
+    if v is not None:
+        out["transmission_weight"] = float(v)
+    v = mat.attr("inputs:alpha")
+    if v is not None:
+        out["geometry_opacity"] = float(v)
+    v = mat.attr("inputs:thinSurface")
+    if v is not None:
+        out["thin_walled"] = 1 if float(v) != 0.0 else 0
+    tex = _material_face_texture(mat, tex_ctx)
+    if tex is not None:
+        out["_face_texture"] = tex
+    return out
+
+
+def _material_of(prim, by_path, tex_ctx=None):
+    """tex_ctx: load(..., face_textures=loader)'s state, or None — then PxrDisneyBsdf reads as default grey and no
+    material carries a per-face texture, as before the keyword existed."""
     target = prim.rels.get("material:binding")
     if isinstance(target, (list, tuple)):
         target = target[0] if target else None
@@ -413,6 +474,8 @@ def _material_of(prim, by_path):
     mat = by_path.get(target)
     if mat is None:
         return DEFAULT_MATERIAL
+    if tex_ctx is not None and any(c.type == "Shader" and c.attr("info:id") == "PxrDisneyBsdf" for c in mat.children):
+        return _disney_material(mat, target, tex_ctx)  # checked before the surface source (usd_import.rs:2583-2594)
     shader = next((c for c in mat.children if c.type == "Shader"), None)
     if shader is not None and shader.attr("info:id") == "UsdPreviewSurface":
         # preview_surface_openpbr (usd_import.rs:2658-2700): OpenPBR::default() with the preview surface's AUTHORED inputs
@@ -431,6 +494,10 @@ def _material_of(prim, by_path):
             out["emission_color"] = e
             if max(float(x) for x in e) > 0.0:
                 out["emission_luminance"] = 1.0
+        if tex_ctx is not None:  # the preview surface may still be the Ptex-driven one (usd_import.rs:2611-2617)
+            tex = _material_face_texture(mat, tex_ctx)
+            if tex is not None:
+                out["_face_texture"] = tex
         return out
     if shader is None or shader.attr("info:id") != "crust:openpbr":
         return DEFAULT_MATERIAL  # no surface shader / unknown id -> default grey (usd_import.rs:2596-2631)
@@ -574,7 +641,8 @@ def _volume_region(prim, world):
                 name=prim.name, **field)
 
 
-def load(path, width=None, height=None, cubic_curves=False, environment_maps=False, volumes=False, path_guiding=False):
+def load(path, width=None, height=None, cubic_curves=False, environment_maps=False, volumes=False, path_guiding=False,
+         face_textures=None):
     """Reads a .usda file into a SceneDesc. width/height override the RenderSettings resolution BEFORE the
     camera is built (the aspect ratio feeds Camera::new; the reference can only do this by editing the USD).
     cubic_curves: decode cubic BasisCurves prims into cubic spans (Geometry::CubicCurves) as the reference's importer
@@ -586,7 +654,14 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
     path_guiding: read crust:pathGuiding, crust:guidingTrainIterations (default 4, at least 1) and crust:guidingProb
     (default 0.5, clamped to [0.1, 0.9] as Renderer::with_guiding clamps it) into desc.settings as guiding,
     guiding_train_iterations, guiding_prob (usd_import.rs:3056-3062, tracer.rs:696-700) — for a host integrator over
-    guiding.GuidingField; the wavefront renderer ignores the keys. By default the description is what it was."""
+    guiding.GuidingField; the wavefront renderer ignores the keys. By default the description is what it was.
+    face_textures: loader(path) -> textures.FaceTexture | None, the host's AssetLoader::load_ptex: asked once per resolved
+    path of a Material's inputs:surfaceMap (an asset beside the layer), negative answers cached too
+    (usd_import.rs:2814-2841). With it a PxrDisneyBsdf material is mapped onto OpenPBR (usd_import.rs:2745-2806), the
+    loaded textures are desc.face_textures, a material that has one carries its index as "_face_texture", the face tables
+    of the meshes under such a material are desc.face_maps, and their geometries carry "face_map" and "face_swapped"
+    (build_face_textures makes the aggregate). By default none of this exists and a Disney material reads as default grey."""
+    tex_ctx = None
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:6] == b"\xfd7zXZ\x00":  # an .xz-compressed stage (scenes/stress.usda.xz: 15 MB of generated text, 0.7 MB packed)
@@ -598,6 +673,10 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
     else:
         meta, roots = parse(raw.decode("utf-8"))
     desc = SceneDesc()
+    if face_textures is not None:
+        import os
+        desc.face_textures, desc.face_maps = [], []
+        tex_ctx = dict(loader=face_textures, dir=os.path.dirname(os.path.abspath(path)), cache={}, textures=desc.face_textures)
 
     by_path = {}
 
@@ -663,13 +742,34 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
         key = (pts.tobytes(), counts.tobytes(), idx.tobytes(), mat.get("_path", id(mat)))
         slot = slot_by_key.get(key)
         if slot is None:
-            tris = _triangulate(counts, idx, pts.shape[0])
+            face_map = None
+            if "_face_texture" in mat:  # want_faces (usd_import.rs:870)
+                tris, faces, slices = _triangulate(counts, idx, pts.shape[0], True)
+                check_face_count(prim, counts, mat)
+            else:
+                tris = _triangulate(counts, idx, pts.shape[0])
             if tris.shape[0] == 0:
                 return None
+            if "_face_texture" in mat:  # one table per distinct mesh, shared by its placements
+                face_map = len(desc.face_maps)
+                desc.face_maps.append((faces, slices))
             slot = len(slots)
-            slots.append(dict(verts=pts, idx=tris, n_place=0, committed=False))
+            slots.append(dict(verts=pts, idx=tris, n_place=0, committed=False, face_map=face_map))
             slot_by_key[key] = slot
         return slot
+
+    def check_face_count(prim, counts, mat):
+        """check_face_count (usd_import.rs:1140-1153): a face id IS a mesh face index, so the counts must match."""
+        n = desc.face_textures[mat["_face_texture"]].n_faces
+        if n != len(counts):
+            import warnings
+            warnings.warn(f"Mesh at {prim.path} has {len(counts)} faces but its per-face texture has {n} — the texture does "
+                          "not match this geometry, so shading will be wrong")
+
+    def bind_faces(geom, face_map, swapped):
+        """World::set_face_map: only geometries whose mesh kept a face table carry the keys."""
+        if face_map is not None:
+            geom["face_map"], geom["face_swapped"] = face_map, bool(swapped)
 
     def committed_proto(slot):
         """MeshArena::committed_scene: the slot as a kernel scene of its own (never baked afterwards)."""
@@ -730,16 +830,17 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
                 warnings.warn(f"nested native instance at {prim.path} skipped")
                 continue
             if prim.type == "Mesh":
-                mat = _material_of(prim, by_path)
+                mat = _material_of(prim, by_path, tex_ctx)
                 slot = intern_mesh(prim, mat)
                 if slot is not None:
-                    parts.append(dict(proto=committed_proto(slot), local=this_local, material=mat, mask=_ray_mask(prim)))
+                    parts.append(dict(proto=committed_proto(slot), local=this_local, material=mat, mask=_ray_mask(prim),
+                                      face_map=slots[slot]["face_map"]))
             elif prim.type == "Sphere":
                 key = ("sphere", float(f32(prim.attr("radius", 1.0))))
                 if key not in sphere_protos:
                     sphere_protos[key] = len(desc.protos)
                     desc.protos.append(dict(radius=key[1]))
-                parts.append(dict(proto=sphere_protos[key], local=this_local, material=_material_of(prim, by_path),
+                parts.append(dict(proto=sphere_protos[key], local=this_local, material=_material_of(prim, by_path, tex_ctx),
                                   mask=_ray_mask(prim)))
             elif prim.type == "PointInstancer":
                 parts.extend(nested_instancer_parts(prim, this_local, _ray_mask(prim), depth + 1))
@@ -822,6 +923,8 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
                 continue  # a zero scale hides an instance
             desc.geoms.append(dict(kind="instance", proto=part["proto"], l2w=affine12(m), mask=part["mask"],
                                    material=part["material"], name=name))
+            # an instance transforms the ray, not the triangles: the prototype's own winding, no swap (usd_import.rs:1659-1663)
+            bind_faces(desc.geoms[-1], part.get("face_map"), False)
 
     def emit_point_instancer(prim, world_xf):
         """emit_point_instancer (usd_import.rs:1832-1876): every placement attaches its prototype's parts, composed
@@ -851,16 +954,24 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
                 desc.volumes.append(reg)
             return world
         if t == "Mesh":  # emit_mesh (usd_import.rs:912-1003)
-            mat = _material_of(prim, by_path)
+            mat = _material_of(prim, by_path, tex_ctx)
             motion = prim.attr("crust:motion:translate")
             if abs(float(_det4(world))) < 1e-12:  # non-invertible placement: baked on the spot, motion ignored
                 pts, counts, idx = prim.attr("points"), prim.attr("faceVertexCounts"), prim.attr("faceVertexIndices")
                 if pts is not None and counts is not None and idx is not None:
                     pts = np.asarray(pts, dtype=np.float32).reshape(-1, 3)
-                    tris = _triangulate(np.asarray(counts), np.asarray(idx), pts.shape[0])
+                    face_map = None
+                    if "_face_texture" in mat:  # usd_import.rs:952-969: attached directly, unswapped
+                        tris, faces, slices = _triangulate(np.asarray(counts), np.asarray(idx), pts.shape[0], True)
+                        check_face_count(prim, counts, mat)
+                    else:
+                        tris = _triangulate(np.asarray(counts), np.asarray(idx), pts.shape[0])
                     if tris.shape[0]:
                         desc.geoms.append(dict(kind="mesh", verts=_xf_point(world, pts), idx=tris, mask=_ray_mask(prim),
                                                material=mat, name=prim.name))
+                        if "_face_texture" in mat:
+                            desc.face_maps.append((faces, slices))
+                            bind_faces(desc.geoms[-1], len(desc.face_maps) - 1, False)
                 return world
             slot = intern_mesh(prim, mat)
             if slot is not None:
@@ -876,10 +987,10 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
                 desc.protos.append(dict(radius=float(radius), center=center))
                 desc.geoms.append(dict(kind="instance", proto=len(desc.protos) - 1, l2w=affine12(_m4()),
                                        l2w_end=affine12(_translation(motion)), mask=_ray_mask(prim),
-                                       material=_material_of(prim, by_path), name=prim.name))
+                                       material=_material_of(prim, by_path, tex_ctx), name=prim.name))
             else:
                 desc.geoms.append(dict(kind="sphere", center=center, radius=radius, mask=_ray_mask(prim),
-                                       material=_material_of(prim, by_path), name=prim.name))
+                                       material=_material_of(prim, by_path, tex_ctx), name=prim.name))
         elif t == "BasisCurves":  # emit_curves (usd_import.rs:2133-2170)
             cubic = prim.attr("type", "cubic") != "linear"
             if cubic and not cubic_curves:
@@ -901,7 +1012,7 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
                         proto["spans"] = spans
                     desc.protos.append(proto)
                     desc.geoms.append(dict(kind="instance", proto=len(desc.protos) - 1, l2w=affine12(world),
-                                           mask=_ray_mask(prim), material=_material_of(prim, by_path), name=prim.name))
+                                           mask=_ray_mask(prim), material=_material_of(prim, by_path, tex_ctx), name=prim.name))
         elif t == "Camera":
             if desc.camera is None:
                 desc.camera = _camera(prim, world, s)
@@ -983,11 +1094,14 @@ def load(path, width=None, height=None, cubic_curves=False, environment_maps=Fal
             if np.linalg.det(m3) < 0.0:  # bake_indices: mirrored placement swaps the winding
                 idx[:, [1, 2]] = idx[:, [2, 1]]
             g.update(kind="mesh", verts=_xf_point(world, sl["verts"]), idx=idx)
+            # the swap exchanges the barycentrics the kernel reports: the face lookup exchanges them back (usd_import.rs:1054-1059)
+            bind_faces(g, sl["face_map"], np.linalg.det(m3) < 0.0)
         else:
             if slot not in proto_of_slot:
                 proto_of_slot[slot] = len(desc.protos)
                 desc.protos.append(dict(verts=sl["verts"], idx=sl["idx"]))
             g.update(kind="instance", proto=proto_of_slot[slot], l2w=affine12(world))
+            bind_faces(g, sl["face_map"], False)  # the prototype's own winding (usd_import.rs:1074-1078)
             if motion is not None:  # transform_end = from_translation(v) * l2w
                 g["l2w_end"] = affine12(_mul(_translation(motion), world))
     if desc.camera is None:
@@ -1138,6 +1252,19 @@ def build_volumes(desc, api):
         return None
     keys = set(api.volumes.region())
     return api.volumes.Volumes([{k: v for k, v in r.items() if k in keys} for r in desc.volumes])
+
+
+def build_face_textures(desc, api):
+    """The aggregate of a description's per-face textures (api.textures.FaceTextures): desc.face_textures and
+    desc.face_maps as they stand, one binding per geometry that carries a face table, and material_texture indexed by
+    geom_id like build_world's material list. None when the description was loaded without face_textures= or no
+    material names a texture."""
+    if not getattr(desc, "face_textures", None):
+        return None
+    T = api.textures
+    bindings = [(gid, g["face_map"], g["face_swapped"]) for gid, g in enumerate(desc.geoms) if "face_map" in g]
+    material_texture = [g["material"].get("_face_texture") for g in desc.geoms]
+    return T.FaceTextures(desc.face_textures, [T.FaceMap(f, s) for f, s in desc.face_maps], bindings, material_texture)
 
 
 def build_world(desc, api, new_material):

@@ -312,7 +312,7 @@ void crt_camera_new(CrtCamera *c, const float lookfrom[3], const float lookat[3]
  * tables are plain arrays of the records above, uploaded by the caller (crt_renderer_new keeps its own copies).
  * INTEGRATION.md binds them as `impl Material for DeviceMaterial` / `impl Light for DeviceLight`. ---- */
 
-/* One call of a Material method: r_in, rec (HitRecord, hittable.rs:10-36; face_id / face_uv are Ptex-only: out of scope),
+/* One call of a Material method: r_in, rec (HitRecord, hittable.rs:10-36; face_id / face_uv are Ptex-only: crt_face_textures.h carries them beside the query),
  * and the method's own argument. 80 bytes. */
 typedef struct CrtShadeQuery {
   float ray_dir[3]; uint32_t material;      /* r_in.direction (unnormalised allowed) | record of the material table   */
