@@ -291,7 +291,7 @@ constexpr int mat_lds_max(int arena) { return (arena - kSobolLdsWords - kRingDwo
 constexpr int kArenaWide = (160 / CRT_SHADE_WIDE_WAVES) * 1024 / 4 - 256;
 static_assert(mat_lds_max(kArenaWide) >= 16 && mat_lds_max(kArenaDwords) >= 16, "the arena holds the Sobol tables, the rings and a material table");
 
-// (The material classes the rings are per: crt_internal.h, material_class.)
+// (The material classes the rings are per: launch_plan.h, material_class.)
 
 // One camera sample (tracer.rs:559-585): PathSampler::new(...).new_domain(tile), filter jitter, lens, primary ray, the
 // K_PATH domain's pattern. g = the sample's global number within the batch: active pixel g % n_act, sample g / n_act.
@@ -452,7 +452,7 @@ __device__ __forceinline__ void generate_segment(const Params &P, const PathSoA 
 // touches none and leaves (cornellbox 1080p: 44 % of the camera rays; 16 of 20 736 escaping rays get past the root). Such
 // a ray used to be written here, fetched, set up and stepped once by the first extend, classified, queued and finished by
 // a miss step of the first shade. Its whole traversal is four slab tests on wave-uniform data, and its origin and
-// direction are in registers here: node_touched (crt_internal.h — the engine's node step, expression for expression)
+// direction are in registers here: node_touched (dev_image.h — the engine's node step, expression for expression)
 // decides, and a ray it calls a miss is finished on the spot with the miss step's arithmetic (escaped_to_sky) and the
 // miss step's counters. The ray IS traced — its traversal is the root step, done where the ray is born — so closest_hit,
 // escaped and the image keep their values. Survivors are appended to the front of the segment with the workgroup's LDS
@@ -1479,7 +1479,7 @@ constexpr int kPipeWaveDwords = kPipePlanes * 256 + 64;
 constexpr int kPipeStageDwords = (kBlock / 64) * kPipeWaveDwords;
 constexpr int kPipeRingDwords = 2 * (int)kPipeRing;
 constexpr int kMatDwords = (int)(sizeof(CrtMaterial) / 4);
-// The rule the host applies (crt_internal.h, shade_pipe_fits): the pipelined instance runs only where the WHOLE material table
+// The rule the host applies (launch_plan.h, shade_pipe_fits): the pipelined instance runs only where the WHOLE material table
 // fits beside its staging blocks; every other scene keeps k_shade and its LDS-resident table. (A lit scene's plane e would
 // add 4 KB of staging and a partitioned scene's four rings 4 KB of rings: neither leaves room for a table.)
 constexpr int kPipeMatMax = (kArenaWide - kSobolLdsWords - kPipeRingDwords - kPipeStageDwords) / kMatDwords;
@@ -2114,7 +2114,7 @@ __global__ __launch_bounds__(kBlock) void k_film_out(const float4 *film, uint32_
 
 // ---------------------------------------------------------------------------------------------
 // The instance table: every instance of the multi-form kernels this build holds, named once — the lists of
-// crt_internal.h expanded to rows {key, kernel}, one typed pointer per kernel signature. A launch plan names keys
+// launch_plan.h expanded to rows {key, kernel}, one typed pointer per kernel signature. A launch plan names keys
 // (plan_launches); a key without a row is an error, never another instance. The host (render.cpp) sees none of it:
 // it gets the pointers from resolve_kernels, the single-form kernels from kStageKernels (render_kernels.h).
 // ---------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #include <cstdlib>
 
 #include "traverse_pool.hip.h"
+#include "../crt_internal.h"
 
 static_assert(crt::dev::kMaxLevels == (int)crt::kMaxInstanceLevels, "commit's nesting limit is the kernels' frame count");
 
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(kBlock, WIDE ? 4 : 3) void occluded_n_kernel(DevSce
 }
 
 // Small flat triangle scenes run the WIDE kernels (four workgroups resident per CU), the others the scene's own split
-// on three: crt_internal.h, select_engine — the one place that decides, from the image, which engine instance runs it.
+// on three: launch_plan.h, select_engine — the one place that decides, from the image, which engine instance runs it.
 // The batched queries report u and v and keep every cold field (kColdAll).
 int query_engine(const DevScene &s, EngineSelect &e) {
   const int rc = select_engine_env(s, e);

@@ -28,12 +28,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../crt_internal.h"
+#include "../launch_plan.h"
 
 namespace crt {
 namespace dev {
 
-// (kBlock, the threads per workgroup: crt_internal.h — the host launchers read it too)
+// (kBlock, the threads per workgroup: dev_image.h — the host launchers read it too)
 // Top of the tree staged in LDS: the first nodes (breadth-first numbering), bounds + child words only (112 of the
 // node's 128 bytes: the traversal does not read `flags`). Two nodes' 16-byte reads collide on banks only when
 // their indices differ by a multiple of 16, the same as with any padded stride.
@@ -166,7 +166,7 @@ __device__ __forceinline__ bool tri_scalar(const RayCtx &r, const float *v /*9: 
 
 // Geometric or interpolated normal of a triangle primitive (prim.rs:76-95). The degenerate-sliver
 // rejection has already happened through Tri4::normal_ok / the explicit check at the call site.
-// A flat triangle's normal is a constant of the committed scene: the upload stores it in the record (crt_internal.h,
+// A flat triangle's normal is a constant of the committed scene: the upload stores it in the record (dev_image.h,
 // flat_tri_normal) and one 16-byte read fetches it — the edges, cross product, square root and three divisions
 // were a sixth of a closest hit's emit step, per ray. SMOOTH: the instance can meet shading normals (kColdUV); the
 // others hold no second arm.

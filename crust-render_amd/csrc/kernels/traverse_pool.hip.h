@@ -66,7 +66,7 @@ namespace dev {
 // deeper than six entries and profits from the node window; instance-heavy scenes stack the parent's entries under
 // the instance's and run +6 % with ten entries and next to no window (profiles/README.md). The host picks the split
 // per scene (DevScene::pool_stack); both fit the same arena.
-constexpr int kPoolStack = CRT_POOL_STACK;       // flat scenes (the three CRT_POOL_STACK* defaults: crt_internal.h)
+constexpr int kPoolStack = CRT_POOL_STACK;       // flat scenes (the three CRT_POOL_STACK* defaults: launch_plan.h)
 constexpr int kPoolStackDeep = CRT_POOL_STACK_DEEP;  // instance-heavy scenes
 // Private part of the stack. sp lives in 8 bits of the ctl word, so LDS part + private part must not exceed 255 with
 // EITHER split: a push at the limit then takes the err path (CRT_ERR_STACK) instead of wrapping into `base`.
@@ -133,7 +133,7 @@ __device__ __forceinline__ int wave_count(bool p) {
   return n;
 }
 
-// COLD: which of the rarely used per-ray fields this instantiation keeps at all (DevScene::cold, crt_internal.h) —
+// COLD: which of the rarely used per-ray fields this instantiation keeps at all (DevScene::cold, dev_image.h) —
 // kColdUV the hit's barycentrics (read only by smooth shading normals and by the batched query's output), kColdNormal
 // the pending normal of a sphere or of a hit below the first instance level, kColdTime the shutter time. They are 4 + 8
 // + 2 of the 28 registers of per-ray cold state a lane carries through every phase; a flat-shaded triangle scene with
@@ -235,7 +235,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
   };
   // What the ray does next: the rest of the leaf's scalar list, else the next stack entry, else leave the tree.
   // A leaf word (kLeafTag set, not the empty marker): the leaf to run packets of, or — direct form, scenes with
-  // DevScene::direct_leaves — the scalar list itself (crt_internal.h). Counts what the packet step counts on entry.
+  // DevScene::direct_leaves — the scalar list itself (dev_image.h). Counts what the packet step counts on entry.
   constexpr bool direct_leaves = DIRECT;  // the caller instantiates the engine per DevScene::direct_leaves
   auto leaf_word = [&](uint32_t e, uint32_t level, uint32_t &cur, uint32_t &cursor, uint32_t &rem) -> uint32_t {
     if (direct_leaves && (e & kDirectLeafTag)) {
@@ -930,7 +930,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
               }
             }
           } else if ((COLD & (int)kColdCurve) != 0 && hd.x == PRIM_CURVE) {  // prim.rs:185-200, curve.rs:17-93
-            // only in the instances built for curve images (kColdCurve: crt_internal.h, select_engine)
+            // only in the instances built for curve images (kColdCurve: launch_plan.h, select_engine)
             const float4 s0 = *reinterpret_cast<const float4 *>(p->d), s1 = *reinterpret_cast<const float4 *>(p->d + 4);
             float t, cnx, cny, cnz;
             if (rounded_cone<ANY>(g0.x, g0.y, g0.z, dx, dy, dz, s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, t_min, closest,
@@ -1111,7 +1111,7 @@ __device__ void traverse_pool(const DevScene &S, uint32_t *lds /* this wave's po
 #ifndef CRT_POOL_ROWS
 #define CRT_POOL_ROWS 2
 #endif
-constexpr int kPoolNodes = CRT_POOL_NODES;          // nodes staged in LDS per workgroup, flat scenes (crt_internal.h)
+constexpr int kPoolNodes = CRT_POOL_NODES;          // nodes staged in LDS per workgroup, flat scenes (launch_plan.h)
 constexpr int kPoolNodesDeep = CRT_POOL_NODES_DEEP;  // ... with the deep stack
 constexpr int kEngineLdsFlat = (kBlock / 64) * pool_lds_dwords<CRT_POOL_ROWS>(kPoolStack) + kPoolNodes * kLdsNodeStride;
 constexpr int kEngineLdsDeep = (kBlock / 64) * pool_lds_dwords<CRT_POOL_ROWS>(kPoolStackDeep) + kPoolNodesDeep * kLdsNodeStride;
@@ -1122,9 +1122,7 @@ constexpr int kEngineLdsDwords = kEngineLdsFlat > kEngineLdsDeep ? kEngineLdsFla
 // more than the shorter LDS stack and the 30 spilled registers cost (cornellbox +4-6 %, veach_mis +9 %, sun_sky +8 % for
 // the per-stage pipeline on it over the fused kernel on three; an instanced city, whose rays stack the parent's entries
 // under the instance's, loses 6 %: profiles/README.md). The renderer and the batched queries pick it per scene
-// (crt_internal.h, wide_split).
-constexpr int kPoolStackWide = CRT_POOL_STACK_WIDE;
-constexpr int kPoolNodesWide = CRT_POOL_NODES_WIDE;  // crt_internal.h
+// (launch_plan.h, wide_split).
 // Round 4: the wide arena's split follows the tree too. A large tree or an instance-heavy scene (DevScene::pool_stack = the
 // deep split's, scene.cpp) trades the node window — 26 of its tens of thousands of nodes — for stack entries: 4 + 12 instead
 // of 3 + 26; and the renderer's kernels, whose rays all carry one mask (UMASK: no mask plane), have one more entry in the
@@ -1132,12 +1130,8 @@ constexpr int kPoolNodesWide = CRT_POOL_NODES_WIDE;  // crt_internal.h
 // entries (measured at 5 + 8 first; 12: PointInstancedMedCity +1.3 %, its root and eight prototype roots then all sit in
 // the window). (Four-wave kernels at 3 + 26 against three-wave ones at 10 + 16, Mray/s: stress 2521 / 2466, the
 // 7 M-triangle scene 3172 / 3307; at 6 + 72 on three waves: stress 2249 — the depth of the LDS part of the stack is what
-// large trees pay for, profiles/README.md.)
-#ifndef CRT_POOL_NODES_WIDE_DEEP
-#define CRT_POOL_NODES_WIDE_DEEP 12
-#endif
-__host__ __device__ constexpr int wide_stack(bool deep_tree, bool umask) { return kPoolStackWide + (deep_tree ? 1 : 0) + (umask ? 1 : 0); }
-__host__ __device__ constexpr int wide_nodes(bool deep_tree) { return deep_tree ? CRT_POOL_NODES_WIDE_DEEP : kPoolNodesWide; }
+// large trees pay for, profiles/README.md.) The split itself is stated once, beside the constants it is made of: the stack
+// entries and the window's nodes of a four-wave kernel in launch_plan.h.
 constexpr int wide_arena(bool deep_tree, bool umask) {
   return (kBlock / 64) * pool_lds_dwords<CRT_POOL_ROWS>(wide_stack(deep_tree, umask), umask) + wide_nodes(deep_tree) * kLdsNodeStride;
 }
@@ -1170,7 +1164,8 @@ __device__ __forceinline__ void run_traversal(const DevScene &S, uint32_t *lds, 
   // kernels are instantiated per DevScene::cold and chosen on the host — several engine copies inside one kernel cost
   // the register allocator more than the leaner copy saves (the fused kernel went from 11 to 89 spilled registers).
   // Any-hit traversal keeps none of that state by construction; the batched queries report u and v and take kColdAll.
-  // The four-wave kernels never meet a direct-leaf scene (crt_internal.h, select_engine).
+  // The plain four-wave kernels (WIDE = 1) never meet a direct-leaf image; their WIDE = 2 instances run nothing else
+  // (launch_plan.h, select_engine, names which).
 #ifndef CRT_WIDE_LEAN
 #define CRT_WIDE_LEAN 1  // the four-wave kernels fetch a packet in stages (LEAN); 0: whole, as the three-wave ones (A/B)
 #endif

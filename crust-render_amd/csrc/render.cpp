@@ -61,7 +61,7 @@ struct Renderer {
   uint32_t *d_state = nullptr, *d_active = nullptr, *d_count = nullptr;
   uint32_t n_act = 0, min_spp = 2;
   float variance_threshold = 0.0f;
-  // Which kernel instances run a batch: plan_launches (crt_internal.h) decides from `in` — the image's engine choice
+  // Which kernel instances run a batch: plan_launches (launch_plan.h) decides from `in` — the image's engine choice
   // (select_engine), the tables, the A/B knobs and this build's switches, filled at creation; the batch's path count and
   // whether it is the stats build, set per batch — and render_lane launches what the instance table below holds for the
   // plan's keys. last_plan: what the LAST batch ran (crt_renderer_pipeline); until the first, the scene's preference.
@@ -294,7 +294,7 @@ struct Renderer {
     return CRT_HIP_OK(hipGetLastError()) ? CRT_OK : fail(CRT_ERR_NO_DEVICE);
   }
 
-  // The launch plan of one lane's batch of n_samples (crt_internal.h, plan_launches), its grid and segment size, and its
+  // The launch plan of one lane's batch of n_samples (launch_plan.h, plan_launches), its grid and segment size, and its
   // buffers (they grow when a batch needs more slots than any before). Sets last_plan / grid for the launches that
   // follow, and p.seg_cap, p.cam_compact, p.root_cull.
   // from P at every plan, so that nothing set after creation leaves the plan stale; the engine choice, mats_kind and
@@ -656,7 +656,7 @@ static CrtRenderer *renderer_new(CrtScene *scene, const CrtMaterial *materials, 
   hipDeviceProp_t prop;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  // Pipeline by scene (crt_internal.h: PlanInputs, wide_split): small flat triangle scenes gain 4-9 % from
+  // Pipeline by scene (launch_plan.h: PlanInputs, wide_split): small flat triangle scenes gain 4-9 % from
   // the fourth wave per SIMD of the per-stage kernels; an instanced city loses 6 % to their four-entry LDS stack, and a
   // scene of analytic spheres only (openpbr_showcase: next to no traversal, all shading) 1 % to the hit records' round
   // trip (profiles/README.md).

@@ -14,10 +14,10 @@ namespace crt {
 
 namespace dev { struct DevMaterial; struct DevMedium; struct PixelRec; struct EnvSlot; }  // behind pointers only
 
-using dev::kBlock;  // threads per workgroup of every launch (crt_internal.h: the traversal library's launches share it)
+using dev::kBlock;  // threads per workgroup of every launch (dev_image.h: the traversal library's launches share it)
 constexpr uint32_t kMaxMedia =(1u << 14) - 1;  // the path state carries a 14-bit compact medium id (PathSoA::d)
 constexpr int kNumberBlock = 1024;              // threads of k_number_media's one workgroup
-constexpr int kClasses = 4;                     // material classes (crt_internal.h, material_class)
+constexpr int kClasses = 4;                     // material classes (launch_plan.h, material_class)
 constexpr uint32_t kPixelTableMaxExtent = 1u << 24;  // a wider frame builds no per-pixel table: (float)px is exact below 2^24
 
 // Path state: struct-of-arrays of 16-byte records, so each plane is read and written with one
@@ -123,7 +123,7 @@ struct Params {
   uint32_t cam_compact;
   // Per-stage launches: generate finishes every camera ray that touches no child box of the root node on the spot — the
   // sky gradient into the staging film, the counters the miss step feeds — and appends only the others to its segment
-  // (generate_segment_cull). Set per batch from the launch plan (crt_internal.h, plan_launches), which holds the rule.
+  // (generate_segment_cull). Set per batch from the launch plan (launch_plan.h, plan_launches), which holds the rule.
   uint32_t root_cull;
   // The library's table of live environments (environment.cpp), read by the mapped-dome instances only (k_shade_env):
   // a CRT_LIGHT_DOME_MAP record names its environment by id. nullptr when the light list holds no such record.

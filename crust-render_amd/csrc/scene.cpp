@@ -322,7 +322,7 @@ Flat::Placed place(Flat &f, const Scene &s) {
     f.packets.push_back(p);
   }
   // Instance slots in the order of the scalar lists (= the builder's leaf order, spatially coherent): the placements
-  // of one leaf sit in consecutive slots, which is what the direct-instance leaf word needs (crt_internal.h).
+  // of one leaf sit in consecutive slots, which is what the direct-instance leaf word needs (dev_image.h).
   std::vector<uint32_t> inst_slot(b.prims.size(), CRT_INVALID_ID);
   {
     uint32_t next_slot = uint32_t(f.instances.size());
@@ -522,7 +522,7 @@ int flatten_image(const Scene &scene, FlatImage &im) {
   }
   // Device form of a node's child words: leaf children carry the leaf tag (bit 31), empty lanes are CRT_INVALID_ID,
   // so the traversal derives everything from the word it has to load anyway and never touches `flags`.
-  // child words carry node and leaf indices below their tag bits (crt_internal.h)
+  // child words carry node and leaf indices below their tag bits (dev_image.h)
   if (f.nodes.size() >= (size_t(1) << 31) || f.leaves.size() >= (size_t(1) << 30) || f.indices.size() >= (size_t(1) << 31)) {
     set_error_text("scene image: %zu nodes / %zu leaves / %zu list entries exceed the child word's index range",
                    f.nodes.size(), f.leaves.size(), f.indices.size());
@@ -560,7 +560,7 @@ int flatten_image(const Scene &scene, FlatImage &im) {
       }
     }
   }
-  // What cold per-ray state a traversal of this image can need (crt_internal.h, kCold*): decided here, where every
+  // What cold per-ray state a traversal of this image can need (dev_image.h, kCold*): decided here, where every
   // primitive of every nested scene is in one array. CRT_COLD=7 keeps everything (A/B, tests).
   {
     uint32_t cold = 0;
@@ -739,7 +739,7 @@ int scene_image_prims(const Scene &scene, std::vector<DevPrim> &out) {
   return CRT_OK;
 }
 
-// Host-only: the renderer's root cull (crt_internal.h, node_touched) asked of the image's root node on the host — the
+// Host-only: the renderer's root cull (dev_image.h, node_touched) asked of the image's root node on the host — the
 // function the generate kernel runs, compiled for the CPU, so a test can hold it against the oracle's traversal.
 int scene_root_touched(const Scene &scene, const float *rays6, size_t n, float t_min, float t_max, uint8_t *out, uint32_t *root) {
   FlatImage im;

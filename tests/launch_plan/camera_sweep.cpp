@@ -1,36 +1,12 @@
-// The camera-trace rule (crust-render_amd/csrc/crt_internal.h: plan_launches, LaunchPlan::camera_trace) on the CPU, driven by
+// The camera-trace rule (crust-render_amd/csrc/launch_plan.h: plan_launches, LaunchPlan::camera_trace) on the CPU, driven by
 // tests/test_camera_trace_plan.py. Plain C++17 against the header alone.
 //   camera_sweep    sweeps the inputs that decide the form, prints the case counts, exit 1 on the first violation
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#include "../../crust-render_amd/csrc/crt_internal.h"
-
-using namespace crt;
-
-#define REQUIRE(cond)                                                        \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      fprintf(stderr, "violated: %s (line %d)\n  case: %s\n", #cond, __LINE__, g_case); \
-      exit(1);                                                               \
-    }                                                                        \
-  } while (0)
-static char g_case[512] = "";
+#include "sweep_common.h"
 
 static const InstanceKey kDeferredKeys[] = {
 #define CRT_KEY_ONLY(family, kernel, ...) CRT_INSTANCE_KEY(family, kernel, __VA_ARGS__),
     CRT_INSTANCES_EXTEND_DEFERRED(CRT_KEY_ONLY)};
 static const InstanceKey kExtendKeys[] = {CRT_INSTANCES_EXTEND(CRT_KEY_ONLY)};
-
-// every field the plan had before the camera trace existed
-static bool same_plan(const LaunchPlan &a, const LaunchPlan &b) {
-  return a.fused == b.fused && a.wide == b.wide && a.tail_at == b.tail_at && a.cam_compact == b.cam_compact && a.root_cull == b.root_cull &&
-         a.shadow == b.shadow && a.noclassify_from == b.noclassify_from && a.ext_cold == b.ext_cold && a.path_cold == b.path_cold &&
-         a.path == b.path && a.extend == b.extend && a.shade == b.shade && a.shade_early == b.shade_early && a.shadow_key == b.shadow_key &&
-         a.volumes == b.volumes && a.volume_key == b.volume_key && a.shadow_volume_key == b.shadow_volume_key && a.slim_state == b.slim_state &&
-         a.shade_slim_key() == b.shade_slim_key();
-}
 
 int main() {
   unsigned long long n_cases = 0, n_planned = 0, n_on = 0, n_on_default = 0, n_on_nocull = 0, n_large_forced = 0;
@@ -66,7 +42,7 @@ int main() {
         rc[k] = plan_launches(q, pl[k]);
       }
       n_cases++;
-      for (int k = 1; k < 5; k++) REQUIRE(rc[k] == rc[0] && same_plan(pl[0], pl[k]));  // the knob changes nothing the plan held before
+      for (int k = 1; k < 5; k++) REQUIRE(rc[k] == rc[0] && same_before_camera_trace(pl[0], pl[k]));  // the knob changes nothing the plan held before
       REQUIRE(!pl[0].camera_trace && pl[0].camera_mode == 0 && pl[0].extend_deferred_key().none());  // 0: the parent's launches
       if (rc[0] != CRT_OK) {
         for (int k = 0; k < 5; k++) REQUIRE(!pl[k].camera_trace && pl[k].extend_deferred_key().none());

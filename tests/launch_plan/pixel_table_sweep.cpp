@@ -1,32 +1,7 @@
-// The per-pixel camera table's rule (crust-render_amd/csrc/crt_internal.h: plan_launches, LaunchPlan::pixel_table) on the
+// The per-pixel camera table's rule (crust-render_amd/csrc/launch_plan.h: plan_launches, LaunchPlan::pixel_table) on the
 // CPU, driven by tests/test_pixel_table_plan.py. Plain C++17 against the header alone.
 //   pixel_table_sweep    sweeps the inputs that decide the form, prints the case counts, exit 1 on the first violation
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#include "../../crust-render_amd/csrc/crt_internal.h"
-
-using namespace crt;
-
-#define REQUIRE(cond)                                                        \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      fprintf(stderr, "violated: %s (line %d)\n  case: %s\n", #cond, __LINE__, g_case); \
-      exit(1);                                                               \
-    }                                                                        \
-  } while (0)
-static char g_case[640] = "";
-
-// every field the plan had before the table existed
-static bool same_plan(const LaunchPlan &a, const LaunchPlan &b) {
-  return a.fused == b.fused && a.wide == b.wide && a.tail_at == b.tail_at && a.cam_compact == b.cam_compact && a.root_cull == b.root_cull &&
-         a.shadow == b.shadow && a.noclassify_from == b.noclassify_from && a.ext_cold == b.ext_cold && a.path_cold == b.path_cold &&
-         a.path == b.path && a.extend == b.extend && a.shade == b.shade && a.shade_early == b.shade_early && a.shadow_key == b.shadow_key &&
-         a.volumes == b.volumes && a.volume_key == b.volume_key && a.shadow_volume_key == b.shadow_volume_key && a.slim_state == b.slim_state &&
-         a.shade_slim_key() == b.shade_slim_key() && a.camera_trace == b.camera_trace && a.camera_mode == b.camera_mode &&
-         a.extend_deferred_key() == b.extend_deferred_key() && a.camera_vertex == b.camera_vertex;
-}
+#include "sweep_common.h"
 
 int main() {
   unsigned long long n_cases = 0, n_planned = 0, n_on = 0, n_on_vertex = 0, n_on_trace = 0, n_on_modes = 0, n_unready = 0, n_lds = 0;
@@ -70,8 +45,8 @@ int main() {
         rc[k] = plan_launches(q, pl[k]);
       }
       n_cases++;
-      REQUIRE(rc_none == rc[0] && same_plan(none, pl[0]));
-      for (int k = 1; k < 3; k++) REQUIRE(rc[k] == rc[0] && same_plan(pl[0], pl[k]));  // the knobs change nothing the plan held before
+      REQUIRE(rc_none == rc[0] && same_before_pixel_table(none, pl[0]));
+      for (int k = 1; k < 3; k++) REQUIRE(rc[k] == rc[0] && same_before_pixel_table(pl[0], pl[k]));  // the knobs change nothing the plan held before
       REQUIRE(!pl[0].pixel_table);  // 0: the computed form
       for (int k = 0; k < 3; k++) {
         // the root from LDS: a camera launch that culls, the root at node 0

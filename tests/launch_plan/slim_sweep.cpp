@@ -1,37 +1,14 @@
-// The slim path state's rule (crust-render_amd/csrc/crt_internal.h: plan_launches, LaunchPlan::slim_state,
+// The slim path state's rule (crust-render_amd/csrc/launch_plan.h: plan_launches, LaunchPlan::slim_state,
 // table_has_no_emitter) on the CPU, driven by tests/test_slim_state_plan.py. Plain C++17 against the header alone.
 //   slim_sweep      sweeps the inputs that decide the form, prints the case counts, exit 1 on the first violation
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <vector>
 
-#include "../../crust-render_amd/csrc/crt_internal.h"
-
-using namespace crt;
-
-#define REQUIRE(cond)                                                        \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      fprintf(stderr, "violated: %s (line %d)\n  case: %s\n", #cond, __LINE__, g_case); \
-      exit(1);                                                               \
-    }                                                                        \
-  } while (0)
-static char g_case[512] = "";
+#include "sweep_common.h"
 
 static const InstanceKey kSlimKeys[] = {
 #define CRT_KEY_ONLY(family, kernel, ...) CRT_INSTANCE_KEY(family, kernel, __VA_ARGS__),
     CRT_INSTANCES_SHADE_PIPE_SLIM(CRT_KEY_ONLY)};
 static const InstanceKey kPipeKeys[] = {CRT_INSTANCES_SHADE_PIPE(CRT_KEY_ONLY)};
-
-// every field the plan had before the slim form existed
-static bool same_plan(const LaunchPlan &a, const LaunchPlan &b) {
-  return a.fused == b.fused && a.wide == b.wide && a.tail_at == b.tail_at && a.cam_compact == b.cam_compact && a.root_cull == b.root_cull &&
-         a.shadow == b.shadow && a.noclassify_from == b.noclassify_from && a.ext_cold == b.ext_cold && a.path_cold == b.path_cold &&
-         a.path == b.path && a.extend == b.extend && a.shade == b.shade && a.shade_early == b.shade_early && a.shadow_key == b.shadow_key;
-}
 
 static CrtMaterial record(uint32_t kind, float r, float g, float b, float lum) {
   CrtMaterial m;
@@ -110,7 +87,7 @@ int main() {
       q.slim_state = 1;
       const int rc_on = plan_launches(q, on);
       n_cases++;
-      REQUIRE(rc_off == rc_on && same_plan(off, on));  // the knob changes nothing the plan held before
+      REQUIRE(rc_off == rc_on && same_before_slim(off, on));  // the knob changes nothing the plan held before
       REQUIRE(!off.slim_state && off.shade_slim_key().none());
       if (rc_on != CRT_OK) { REQUIRE(!on.slim_state && on.shade_slim_key().none()); continue; }
       n_planned++;

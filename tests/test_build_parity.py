@@ -247,7 +247,7 @@ _ENGINE_KNOBS = ("CRT_DIRECT_LEAVES", "CRT_DIRECT_INST", "CRT_WIDE", "CRT_POOL_S
 
 
 def test_every_knob_combination_selects_an_engine_that_can_decode_the_image(crt, monkeypatch):
-    """The engine-vs-image class, closed in one place (crt_internal.h, select_engine): rounds 2 and 3 each lost a GPU box
+    """The engine-vs-image class, closed in one place (launch_plan.h, select_engine): rounds 2 and 3 each lost a GPU box
     to a traversal-engine instance meeting an image form it was not built for (profiles/README.md, "The r02f abort",
     "The r03w fault": direct child words read by the four-wave kernels, which carry no direct-leaf engine). For every
     combination of the A/B knobs that shape the image or the choice, on the six scene recipes, what a launch in this

@@ -1,4 +1,4 @@
-"""The camera-trace rule WITHOUT a GPU (crust-render_amd/csrc/crt_internal.h: plan_launches, LaunchPlan::camera_trace,
+"""The camera-trace rule WITHOUT a GPU (crust-render_amd/csrc/launch_plan.h: plan_launches, LaunchPlan::camera_trace,
 extend_deferred_key): tests/launch_plan/camera_sweep.cpp compiled as plain C++ and run as a child process.
 
 Where the plan says so, one launch of k_camera generates, culls and traces a batch's camera rays and the first extend is

@@ -1,4 +1,4 @@
-"""The camera-vertex rule WITHOUT a GPU (crust-render_amd/csrc/crt_internal.h: plan_launches, LaunchPlan::camera_vertex):
+"""The camera-vertex rule WITHOUT a GPU (crust-render_amd/csrc/launch_plan.h: plan_launches, LaunchPlan::camera_vertex):
 tests/launch_plan/camera_vertex_sweep.cpp compiled as plain C++ and run as a child process.
 
 Where the plan says so, k_camera_vertex shades the first vertex of a camera path in the lane that traced its ray, and the

@@ -1,4 +1,4 @@
-"""The unit normal a flat triangle carries in the device image (crt_internal.h, flat_tri_normal; scene.cpp,
+"""The unit normal a flat triangle carries in the device image (dev_image.h, flat_tri_normal; scene.cpp,
 flatten_image), checked on the host: crt_scene_image_check re-evaluates every stored normal, and the records themselves
 (crt_scene_image_prims) are compared here with a float32 evaluation of prim.rs:76-95 that shares no code with the
 library. No GPU."""
@@ -8,7 +8,7 @@ import pytest
 import packet_cases as pc
 
 f32 = np.float32
-SMOOTH_TAG = 0x7FA5A5A5  # crt_internal.h, kSmoothNormalTag: a signalling NaN, which no division returns
+SMOOTH_TAG = 0x7FA5A5A5  # dev_image.h, kSmoothNormalTag: a signalling NaN, which no division returns
 
 
 def _mixed_mesh():

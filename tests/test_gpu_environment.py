@@ -191,7 +191,7 @@ def _check_render(crt, desc, spp, name, want_class=None):
     err = np.abs(dimg - ref) / np.maximum(1.0, np.abs(ref))
     assert err.max() <= 1e-5, (name, err.max())  # the tolerance of test_forward_equals_reference_gather_within_float_association
     if want_class is not None:  # the look that selects the kernel instance is in the table the renderer was given
-        def cls(m):  # crt_internal.h, material_class
+        def cls(m):  # launch_plan.h, material_class
             if m.kind == crt.MAT_EMISSIVE:
                 return 0
             if m.transmission_weight > 0 or m.subsurface_weight > 0:
@@ -209,7 +209,7 @@ def test_domelight_render_equals_the_hooked_reference_integrator(crt, oracle):
     assert np.isfinite(img).all() and img.max() > 0
 
 
-# Which shade instance a light list with a mapped dome runs follows from the material table (crt_internal.h, plan_launches: the k_shade_env rows):
+# Which shade instance a light list with a mapped dome runs follows from the material table (launch_plan.h, plan_launches: the k_shade_env rows):
 # simple materials k_shade_env<0, true> (derived records, the default) or <0, false> (CRT_MAT_DERIVED=0); any coat, fuzz or
 # thin-film material <1, false>; any material with an interior medium <2, false>. domelight itself is all simple, so each
 # of the other three is reached by changing one look of that scene.

@@ -1,5 +1,5 @@
 """What a batch launches, counted: crt_renderer_profile / crt_renderer_profile_read time every launch of a batch by class
-(extend, shade, shadow, other) and count them. The counts follow from the launch plan (crt_internal.h, plan_launches) and
+(extend, shade, shadow, other) and count them. The counts follow from the launch plan (launch_plan.h, plan_launches) and
 render_lane's loop: per stage with depth limit d and the tail from bounce t, extend = shade = min(d + 1, t); shadow
 equals that on a lit scene under a strategy that samples the lights, else 0; other = generate + the tail launch when
 t <= d + the film fold. Fused: one launch of class extend (the path-loop kernel), one other (the fold). The stats build

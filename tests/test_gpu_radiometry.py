@@ -71,7 +71,7 @@ def test_device_matches_the_oracle_and_the_closed_form(crt, monkeypatch, name, p
             assert counters == want_counters, (name, s, frame, dict(zip(COUNTERS, zip(counters, want_counters))))
             bad = np.argwhere(img.view(np.uint32) != want_img.view(np.uint32))
             assert bad.shape[0] == 0, (name, s, frame, bad.shape[0], bad[:3])
-            # no fused instance carries the lights at infinity (crt_internal.h, launch plan): of these scenes the fused
+            # no fused instance carries the lights at infinity (launch_plan.h, launch plan): of these scenes the fused
             # kernel takes the emissive interiors, asked for or by default, and every scene with a dome runs per stage
             at_infinity = any(l["kind"] in ("dome", "distant") for l in case.build(s, frame).lights)
             if fused is not None:

@@ -172,7 +172,7 @@ def test_tile_shards_reassemble_the_single_gpu_image(crt):
                                              ("nested_instancing", 64, 36, 6), ("stress", 96, 54, 6),
                                              ("motionblur", 96, 54, 4)])
 def test_the_three_pipelines_agree(crt, tmp_path, scene, w, h, depth):
-    """The renderer picks its pipeline per scene and batch (crt_internal.h, plan_launches): the fused path-loop kernel on
+    """The renderer picks its pipeline per scene and batch (launch_plan.h, plan_launches): the fused path-loop kernel on
     three workgroups per CU, or one launch per stage with the four-workgroups-per-CU traversal kernels for large batches of
     small flat triangle scenes. All combinations (fused; per-stage with either engine split; switching between batches of
     one render) are the same device functions: identical image and counters on a lit scene with interior media, a

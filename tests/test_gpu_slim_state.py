@@ -1,5 +1,5 @@
 """The slim path state between two launches of the pipelined shade kernel (pathtrace.hip, k_shade_pipe<DRV, true>;
-crt_internal.h, LaunchPlan::slim_state) against the full one (CRT_SLIM_STATE=0).
+launch_plan.h, LaunchPlan::slim_state) against the full one (CRT_SLIM_STATE=0).
 
 Where nothing in the material table emits, a pipelined launch hands the next one 48 bytes per path instead of 64: no
 radiance (it is +0), no depth words (they follow from the bounce number), the hit word through the hit ring. What a path

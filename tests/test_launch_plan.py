@@ -1,4 +1,4 @@
-"""The renderer's launch plan WITHOUT a GPU: plan_launches (crust-render_amd/csrc/crt_internal.h) decides once per batch
+"""The renderer's launch plan WITHOUT a GPU: plan_launches (crust-render_amd/csrc/launch_plan.h) decides once per batch
 which kernel instances run it; kernels/pathtrace.hip only looks the named instances up in its table, render.cpp loops. Here the
 function is compiled as plain C++ (tests/launch_plan/plan_sweep.cpp, own main) and run as a child process.
 
@@ -58,6 +58,8 @@ def test_every_plan_of_the_sweep_keeps_the_rules(tmp_path, name):
     assert int(got["cases"]) > 10_000_000 and int(got["planned"]) > 10_000_000
     assert int(got["planned"]) + int(got["refused"]) == int(got["cases"])
     assert int(got["engines"]) >= 90 and int(got["noengine"]) > 0  # the grid reaches refusals of select_engine too
+    if name == "default":  # the figures the sweeps that share the grid pin too (test_face_plan.py, test_volume_render.py)
+        assert (int(got["engines"]), int(got["cases"])) == (120, 16312320), got
 
 
 def test_the_plan_reproduces_the_decision_table_of_the_ladders(tmp_path):

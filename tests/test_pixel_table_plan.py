@@ -1,4 +1,4 @@
-"""The per-pixel camera table's rule WITHOUT a GPU (crust-render_amd/csrc/crt_internal.h: plan_launches,
+"""The per-pixel camera table's rule WITHOUT a GPU (crust-render_amd/csrc/launch_plan.h: plan_launches,
 LaunchPlan::pixel_table): tests/launch_plan/pixel_table_sweep.cpp compiled as plain C++ and run as a child process.
 
 Where the plan says so, the camera launch (k_camera or k_camera_vertex) reads what a sample owes to its pixel alone from

@@ -1,4 +1,4 @@
-"""The renderer's root cull as a host function (crt.h, crt_scene_root_touched_n; crt_internal.h, node_touched) against
+"""The renderer's root cull as a host function (crt.h, crt_scene_root_touched_n; dev_image.h, node_touched) against
 the oracle's traversal. No GPU: the function the generate kernel runs is compiled for the CPU from the same source.
 
 The rule: a camera ray is finished in generate iff it touches no child box of the image's root node. The oracle says the

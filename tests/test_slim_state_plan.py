@@ -1,4 +1,4 @@
-"""The slim path state's rule WITHOUT a GPU (crust-render_amd/csrc/crt_internal.h: plan_launches, LaunchPlan::slim_state,
+"""The slim path state's rule WITHOUT a GPU (crust-render_amd/csrc/launch_plan.h: plan_launches, LaunchPlan::slim_state,
 table_has_no_emitter): tests/launch_plan/slim_sweep.cpp compiled as plain C++ and run as a child process.
 
 The pipelined shade kernel's launches hand each other a 48-byte path state where the plan says so. The sweep crosses what
