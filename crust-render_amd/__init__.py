@@ -183,6 +183,8 @@ ABI_SYMBOLS = [
 # include/crt_render_volumes.h: the entry point of volume renders, declared beside crt.h (whose 84 declarations the list
 # above mirrors) and exported by the same library.
 ABI_SYMBOLS_RENDER_VOLUMES = ["crt_renderer_set_volumes"]
+# include/crt_render_guiding.h: the one entry point that binds a guiding field to the wavefront renderer.
+ABI_SYMBOLS_RENDER_GUIDING = ["crt_renderer_set_guiding"]
 # include/crt_scene_image.h: the host-only hand-out of the scene image's arrays, declared beside crt.h for the same reason.
 ABI_SYMBOLS_SCENE_IMAGE = ["crt_scene_image_array"]
 # include/crt_guiding.h: the path guiding field (guiding.py), declared beside crt.h for the same reason.
@@ -326,6 +328,8 @@ def lib():
         L.crt_volumes_density_n.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, vp]
         L.crt_volumes_transmittance_n.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.crt_volumes_sample_n.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "crt_renderer_set_guiding"):  # guided renders (absent from older A/B variant libraries)
+        L.crt_renderer_set_guiding.argtypes = [vp, vp]
     if hasattr(L, "crt_renderer_set_volumes"):  # volume renders (absent from older A/B variant libraries)
         L.crt_renderer_set_volumes.argtypes = [vp, vp]
     if hasattr(L, "crt_guiding_new"):  # the path guiding field (guiding.py; absent from older A/B variant libraries)
@@ -866,6 +870,7 @@ class Renderer:
             raise CrtError(-1, "crt_renderer_new")
         self.n_pix = lib().crt_renderer_pixel_count(self.h)
         self.volumes = None  # the bound aggregate (set_volumes)
+        self.guiding = None  # the bound guiding field (set_guiding)
 
     def __del__(self):
         try:
@@ -888,6 +893,17 @@ class Renderer:
         uploaded inside the call. Where no region is crossed the image equals the unbound renderer's bit for bit."""
         _check(lib().crt_renderer_set_volumes(self.h, vol.h if vol is not None else None), "crt_renderer_set_volumes")
         self.volumes = vol
+
+    def set_guiding(self, field):
+        """Binds a trained guiding field (guiding.GuidingField) for the batches that follow, or detaches it (None): the
+        guided pass of render_guided in the wavefront renderer (crt_render_guiding.h, crt_renderer_set_guiding) — at
+        secondary surface vertices where the field is trained the bounce is sample_bounce_direction and the NEE weight
+        competes with the mixture pdf. The renderer trains nothing: whoever owns the field updates it (field.update,
+        between render calls; the next render_samples reads the new image). The renderer keeps the field alive. With an
+        untrained field image and counters are those of the unbound renderer. Not beside volumes or textures, not in the
+        stats build."""
+        _check(lib().crt_renderer_set_guiding(self.h, field.h if field is not None else None), "crt_renderer_set_guiding")
+        self.guiding = field
 
     def set_face_textures(self, ft):
         """Binds a per-face texture aggregate (textures.FaceTextures: its bindings keyed by this renderer's geom_ids, its
@@ -970,13 +986,14 @@ class Renderer:
         shaded their first vertex, and the first extend and shade ran over the rays it deferred; pixel_table: that launch
         read each sample's per-pixel words from the table the renderer filled at creation; cull_root_lds: its root cull
         read the root node from the launch's LDS window; face_textures: the batch was a textured render (set_face_textures:
-        the FACES extend and shade instances ran)."""
+        the FACES extend and shade instances ran); guiding: the batch was a guided render (set_guiding: the GUIDED shade
+        instances ran)."""
         out = (C.c_uint32 * 3)()
         _check(lib().crt_renderer_pipeline(self.h, out), "crt_renderer_pipeline")
         return dict(fused=bool(out[0]), wide=bool(out[1] & 1), shade_pipe=bool(out[1] & 2), root_cull=bool(out[1] & 4),
                     slim_state=bool(out[1] & 8), volumes=bool(out[1] & 16), camera_trace=bool(out[1] & 32),
                     camera_vertex=bool(out[1] & 64), pixel_table=bool(out[1] & 128), cull_root_lds=bool(out[1] & 256),
-                    face_textures=bool(out[1] & 512), grid=int(out[2]))
+                    face_textures=bool(out[1] & 512), guiding=bool(out[1] & 1024), grid=int(out[2]))
 
     def lanes(self):
         """Sub-batches (own buffers, own HIP stream) the last batch ran as (crt.h, crt_renderer_lanes)."""

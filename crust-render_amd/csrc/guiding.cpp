@@ -11,6 +11,7 @@
 //
 // Departures from the reference, all named in DESIGN.md §2: the configuration is checked (crt_guiding_new), the depths
 // are capped, and everything guiding.hip.h lists.
+#include <atomic>
 #include <cstring>
 #include <new>
 
@@ -234,6 +235,9 @@ struct CrtGuiding {
   std::mutex mu;
   void *d_image = nullptr;  // uploaded on first device use
   bool stale = true;        // the image was rebuilt since the upload
+  // the caller's reference and one per renderer the field is bound to (crt_renderer_set_guiding): crt_guiding_free drops
+  // the caller's, the last one frees
+  std::atomic<int> refs{1};
 };
 
 using namespace crt;
@@ -323,20 +327,23 @@ int crt_guiding_stats(const CrtGuiding *g, CrtGuidingStats *out) {
 #ifdef CRT_GUIDING_HOST_ONLY
 void crt_guiding_free(CrtGuiding *g) { delete g; }
 #else
-void crt_guiding_free(CrtGuiding *g) {
-  if (!g) return;
-  if (g->d_image) {
-    (void)hipDeviceSynchronize();  // nothing that was handed the image may still be reading it
-    (void)hipFree(g->d_image);
-  }
-  delete g;
-}
+void crt_guiding_free(CrtGuiding *g) { guiding_release(g); }
 #endif
 
 }  // extern "C"
 
 #ifndef CRT_GUIDING_HOST_ONLY
 namespace crt {
+
+void guiding_retain(CrtGuiding *g) { if (g) g->refs.fetch_add(1, std::memory_order_relaxed); }
+void guiding_release(CrtGuiding *g) {
+  if (!g || g->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  if (g->d_image) {
+    (void)hipDeviceSynchronize();  // nothing that was handed the image may still be reading it
+    (void)hipFree(g->d_image);
+  }
+  delete g;
+}
 
 int guiding_device(CrtGuiding *g, dev::GuideView &out) {
   std::lock_guard<std::mutex> lock(g->mu);

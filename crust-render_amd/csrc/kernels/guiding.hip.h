@@ -198,12 +198,17 @@ __device__ __forceinline__ bool guide_field_sample(const GuideView &V, V3 pos, f
   dir = guide_canonical_to_dir(p);
   return true;
 }
-__device__ __forceinline__ float guide_field_pdf(const GuideView &V, V3 pos, V3 dir, bool &trained) {
-  const uint32_t root = guide_dtree_at(V, pos);
-  trained = guide_trained(V, root);
+// GuidingField::pdf behind the spatial descent: the D-tree `root` governs the position (shade_segment shares one descent
+// between this and the bounce)
+__device__ __forceinline__ float guide_field_pdf_at(const GuideView &V, uint32_t root, V3 dir) {
   float p[2];
   guide_dir_to_canonical(dir, p);
   return guide_dtree_pdf(V, root, p);
+}
+__device__ __forceinline__ float guide_field_pdf(const GuideView &V, V3 pos, V3 dir, bool &trained) {
+  const uint32_t root = guide_dtree_at(V, pos);
+  trained = guide_trained(V, root);
+  return guide_field_pdf_at(V, root, dir);
 }
 
 }  // namespace dev
@@ -221,24 +226,31 @@ constexpr uint32_t kGuidedTrained = 4u, kGuidedFromGuide = 8u;  // CrtScatterSam
 
 // Material::make_ray: openpbr.rs:1186-1200 — across a continuous-transmission interface the origin is p + wi * 1e-4 and
 // the ray carries the interior only on the way in and only if the material has one; Emissive: material.rs:79-81.
+// RESOLVE: the flag is checked against the material's interior here (the seam's answer); otherwise it says "enters through
+// the front face" as mat_scatter's does, and the caller resolves it through its media table (shade_segment).
+template <bool SIMPLE = false, bool RESOLVE = true>
 __device__ __forceinline__ void guide_make_ray(const CrtMaterial &m, const HitRec &rec, V3 wi, V3 &origin, bool &medium) {
   origin = rec.p;
   medium = false;
-  if (m.kind == CRT_MAT_EMISSIVE) return;
+  if (SIMPLE || m.kind == CRT_MAT_EMISSIVE) return;  // a simple-material table holds no transmission anywhere
   if (transmission_is_continuous(m) && dot(rec.normal, wi) < 0.0f) {
     origin = rec.p + wi * 1e-4f;
     if (rec.front_face) {
-      DevMedium med;
-      medium_from_material(m, med);
-      medium = med.present != 0;
+      medium = true;
+      if (RESOLVE) {
+        DevMedium med;
+        medium_from_material(m, med);
+        medium = med.present != 0;
+      }
     }
   }
 }
 // Material::scatter_importance as the seam answers it (shade_seam.hip, k_seam_scatter): the medium flag only if the
-// material has an interior
+// material has an interior (RESOLVE, as above)
+template <bool SIMPLE = false, bool RESOLVE = true>
 __device__ __forceinline__ bool guide_plain_scatter(const CrtMaterial &m, V3 rd, const HitRec &rec, Sampler dom, Scatter &sc, const uint32_t *tab) {
-  const bool some = mat_scatter<false>(m, rd, rec, dom, sc, tab);
-  if (some && sc.medium) {
+  const bool some = mat_scatter<SIMPLE>(m, rd, rec, dom, sc, tab);
+  if (RESOLVE && some && sc.medium) {
     DevMedium med;
     medium_from_material(m, med);
     sc.medium = med.present != 0;
@@ -246,13 +258,21 @@ __device__ __forceinline__ bool guide_plain_scatter(const CrtMaterial &m, V3 rd,
   return some;
 }
 
-// sample_bounce_direction, tracer.rs:777-826. v is the VERTEX domain. flags: kGuidedTrained | kGuidedFromGuide.
-__device__ __forceinline__ bool guide_sample_bounce(const GuideView &V, const CrtMaterial &m, V3 rd, const HitRec &rec, Sampler v, Scatter &sc,
-                                                    uint32_t &flags, const uint32_t *tab) {
+// sample_bounce_direction, tracer.rs:777-826, behind the spatial descent: `root` is guide_dtree_at(V, rec.p) and `trained`
+// guide_trained(V, root) — the caller made them once and shares them with the NEE pdf (shade_segment), or just now
+// (guide_sample_bounce below). v is the VERTEX domain. flags: kGuidedTrained | kGuidedFromGuide. One text for the seam
+// kernel (RESOLVE) and the guided shade kernels (SIMPLE as the instance's): both read raw material records, the view
+// every guided instance's table hands out (MatTable<false>: MatRaw).
+// The text is the seam's as it stood, with its two mat_eval sites, so that the seam kernel keeps its registers and stays
+// without scratch. A single-site form (one pass chooses wi, then evaluates; a second pass for the guide draw the material
+// cannot evaluate) was compiled once while this was written and not kept: in the seam kernel the compiler then left mat_eval
+// out of line (128 -> 153 VGPRs, 80 bytes of scratch). Whether it would shrink the guided shade instances is not known.
+template <bool SIMPLE, bool RESOLVE>
+__device__ __forceinline__ bool guide_sample_bounce_at(const GuideView &V, uint32_t root, bool trained, const CrtMaterial &m, V3 rd, const HitRec &rec,
+                                                       Sampler v, Scatter &sc, uint32_t &flags, const uint32_t *tab) {
   const Sampler bsdf_dom = new_domain(v, kDomainBsdf);
-  const uint32_t root = guide_dtree_at(V, rec.p);
   flags = 0;
-  if (!guide_trained(V, root)) return guide_plain_scatter(m, rd, rec, bsdf_dom, sc, tab);
+  if (!trained) return guide_plain_scatter<SIMPLE, RESOLVE>(m, rd, rec, bsdf_dom, sc, tab);
   flags = kGuidedTrained;
   const float alpha = V.alpha;
   float gs[4];
@@ -264,9 +284,9 @@ __device__ __forceinline__ bool guide_sample_bounce(const GuideView &V, const Cr
       const V3 wi = guide_canonical_to_dir(p);
       V3 value;
       float p_bsdf;
-      if (mat_eval<false>(m, rd, rec, wi, value, p_bsdf)) {
+      if (mat_eval<SIMPLE>(m, rd, rec, wi, value, p_bsdf)) {
         sc.pdf = rmax(alpha * p_guide + (1.0f - alpha) * p_bsdf, 1e-4f);
-        guide_make_ray(m, rec, wi, sc.origin, sc.medium);
+        guide_make_ray<SIMPLE, RESOLVE>(m, rec, wi, sc.origin, sc.medium);
         sc.dir = wi;
         sc.value = value;
         sc.delta = false;
@@ -274,9 +294,9 @@ __device__ __forceinline__ bool guide_sample_bounce(const GuideView &V, const Cr
         return true;
       }
     }
-    return guide_plain_scatter(m, rd, rec, bsdf_dom, sc, tab);  // no continuous component: pure BSDF sampling
+    return guide_plain_scatter<SIMPLE, RESOLVE>(m, rd, rec, bsdf_dom, sc, tab);  // no continuous component: pure BSDF sampling
   }
-  if (!guide_plain_scatter(m, rd, rec, bsdf_dom, sc, tab)) return false;
+  if (!guide_plain_scatter<SIMPLE, RESOLVE>(m, rd, rec, bsdf_dom, sc, tab)) return false;
   if (sc.delta) {  // only this branch reaches the delta lobe: the coin scaled its selection probability by 1 - alpha
     sc.value = sc.value / (1.0f - alpha);
     return true;
@@ -284,13 +304,19 @@ __device__ __forceinline__ bool guide_sample_bounce(const GuideView &V, const Cr
   const V3 wi = normalize(sc.dir);
   V3 value;
   float p_bsdf;
-  if (mat_eval<false>(m, rd, rec, wi, value, p_bsdf)) {
+  if (mat_eval<SIMPLE>(m, rd, rec, wi, value, p_bsdf)) {
     float p[2];
     guide_dir_to_canonical(wi, p);
     const float p_guide = guide_dtree_pdf(V, root, p);
     sc.pdf = rmax(alpha * p_guide + (1.0f - alpha) * sc.pdf, 1e-4f);
   }
   return true;
+}
+// ... with its own descent: the seam's entry (kernels/guiding_seam.hip, tests/host_shade/guiding_host.cpp)
+__device__ __forceinline__ bool guide_sample_bounce(const GuideView &V, const CrtMaterial &m, V3 rd, const HitRec &rec, Sampler v, Scatter &sc,
+                                                    uint32_t &flags, const uint32_t *tab) {
+  const uint32_t root = guide_dtree_at(V, rec.p);
+  return guide_sample_bounce_at<false, true>(V, root, guide_trained(V, root), m, rd, rec, v, sc, flags, tab);
 }
 
 }  // namespace dev

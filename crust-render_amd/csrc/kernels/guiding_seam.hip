@@ -6,7 +6,8 @@
 // vectors. The view of the image (pointers, counts, bounds, alpha) is a kernel argument: wave-uniform, scalar registers.
 // A descent is a chain of dependent loads — at most 33 16-byte S-nodes, then at most 32 D-nodes of two 16-byte loads each
 // that go out together; nothing here hides that latency but the other waves of the SIMD. The guided bounce calls the same
-// mat_scatter<false> / mat_eval<false> the shading seam's kernels call. The wavefront renderer runs none of this.
+// mat_scatter<false> / mat_eval<false> the shading seam's kernels call. The wavefront renderer runs none of these
+// kernels: its guided shade instances (pathtrace.hip, k_shade_guided) call the same guide_sample_bounce_at.
 // Compile with -ffp-contract=off (dmath.hip.h).
 #define CRT_GUIDING_BOUNCE
 #include "guiding.hip.h"

@@ -29,10 +29,12 @@
 // renderer that launches them — buffers, lanes, the bounce loop, the C ABI — is ../render.cpp.
 #include <cstddef>
 
+#define CRT_GUIDING_BOUNCE  // guiding.hip.h (first included by render_kernels.h) with the guided bounce: k_shade_guided
 #include "../render_kernels.h"
 #include "camera_pixel.hip.h"
 #include "shade.hip.h"
 #include "faces.hip.h"
+#include "guiding.hip.h"
 #include "traverse_camera.hip.h"
 #include "traverse_pool.hip.h"
 #include "vertex_simple.hip.h"
@@ -793,15 +795,23 @@ __device__ __forceinline__ const MatFace &view_of(const MV &, const MatFace &fv)
 // behind a kVolScatter hit word — its values are loaded into the variables of the tail below, which compacts, queues the
 // shadow request and stages as for any vertex; the vertex code is skipped. Every shadow request's K_NEE_SHADOW seed goes
 // to qseed (k_shadow_volume walks the segment with it).
-template <int MATS, int INF, bool LIT, int ARENA, bool DRV, bool VOL = false, bool FACES = false>
+// GUIDED: the instances of guided renders (k_shade_guided), render_pass(.., Some(&GuidingContext{field, training: false}))
+// — the guided-forward form of DESIGN.md §2. At a surface vertex with a previous vertex (tracer.rs:1386: never the camera
+// vertex, never the vertex behind an interior-medium scatter) ONE spatial descent finds the D-tree governing rec.p; where
+// that tree is trained the NEE weight's bounce pdf is the mixture (tracer.rs:1432-1440) and the bounce is
+// sample_bounce_direction (tracer.rs:777-826, guide_sample_bounce_at), whose mixture pdf travels on as n_ppdf. The view GV
+// is the kernel's argument: alpha, bounds, counts and array bases are wave-uniform. No loop, LDS word or barrier is new.
+template <int MATS, int INF, bool LIT, int ARENA, bool DRV, bool VOL = false, bool FACES = false, bool GUIDED = false>
 __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S, const PathSoA &N, const HitSoA &H,
                                               const ShadowSoA &Q, Counters *C, int cur, float4 *staging,
                                               uint32_t *sobol_tab /* ARENA dwords: Sobol tables, then the material table */,
                                               bool first /* camera paths whose plane c was not written (generate_segment) */,
                                               bool all_pending = false /* no CLASSIFY pass: every path takes the vertex step */,
                                               uint32_t *qseed = nullptr /* VOL: one word per shadow-queue slot */,
-                                              const FaceView *FV = nullptr, const uint4 *fplane = nullptr /* FACES */) {
+                                              const FaceView *FV = nullptr, const uint4 *fplane = nullptr /* FACES */,
+                                              const GuideView *GV = nullptr /* GUIDED */) {
   constexpr bool MEDIA = MATS == 2, SIMPLE = MATS == 0;
+  static_assert(!GUIDED || (!VOL && !FACES && !DRV), "guided renders: raw records, neither volumes nor textures");
   static_assert(SIMPLE || !DRV, "the derived record covers what a simple-material table reads (shade.hip.h)");
   typedef MatTable<DRV> Table;
   // Two of round 3's forms are compiled only into the instances that have registers to spare: the lit four-wave shade
@@ -1142,6 +1152,13 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
             emit_here = emitted;
           }
           const V3 ba = beta * atten;
+          // guiding_here (tracer.rs:1386) and the one descent NEE and the bounce share
+          uint32_t g_root = kGuideNoChild;
+          bool g_trained = false;
+          if (GUIDED && prev_valid) {
+            g_root = guide_dtree_at(*GV, rec.p);
+            g_trained = guide_trained(*GV, g_root);
+          }
 
           // === 1. direct lighting by light sampling (tracer.rs:1394-1445) ===
           if (LIT && P.strategy != CRT_STRATEGY_BSDF && n_lights > 0) {
@@ -1161,6 +1178,8 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
               V3 brdf_value; float brdf_pdf;
               V3 nee = splat(0.0f);
               if (mat_eval<SIMPLE>(view_of(mat, fmat), rd, rec, ls.direction, brdf_value, brdf_pdf)) {
+                // the competing strategy is the bounce sampler: the guide / BSDF mixture where the field is trained here
+                if (GUIDED && g_trained) brdf_pdf = GV->alpha * guide_field_pdf_at(*GV, g_root, ls.direction) + (1.0f - GV->alpha) * brdf_pdf;
                 const float weight = light_weight(P.strategy, light_pdf, brdf_pdf);
                 V3 c = (ls.radiance * brdf_value) * cosine;
                 c = c * splat(1.0f);  // shadow_tr == ONE when unoccluded
@@ -1173,7 +1192,14 @@ __device__ __forceinline__ void shade_segment(const Params &P, const PathSoA &S,
 
           // === 2. indirect lighting by BSDF sampling (tracer.rs:1459-1523) ===
           Scatter sample;
-          if (mat_scatter<SIMPLE>(view_of(mat, fmat), rd, rec, new_domain(vdom, K_BSDF), sample, sobol_tab)) {
+          bool scattered;
+          if (GUIDED) {  // off the vertex domain: K_BSDF and K_GUIDE are derived inside (an untrained vertex: mat_scatter on K_BSDF)
+            uint32_t g_flags;
+            scattered = guide_sample_bounce_at<SIMPLE, false>(*GV, g_root, g_trained, mat.raw(), rd, rec, vdom, sample, g_flags, sobol_tab);
+          } else {
+            scattered = mat_scatter<SIMPLE>(view_of(mat, fmat), rd, rec, new_domain(vdom, K_BSDF), sample, sobol_tab);
+          }
+          if (scattered) {
             const V3 dir = normalize(sample.dir);
             const float cosine = sample.delta ? 1.0f : fabs_(dot(rec.normal, dir));
             const V3 factor = (sample.value * cosine) / sample.pdf;
@@ -1293,6 +1319,17 @@ __global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_faces(Params 
   __shared__ uint32_t sobol_tab[kArenaDwords];
   shade_segment<MATS, INF, LIT, kArenaDwords, false, false, true>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0, (first & 2) != 0,
                                                                   nullptr, &F, fplane);
+}
+
+// The instances of guided renders (LaunchPlan::guided), instantiated as k_shade_vol's: three waves, raw material records.
+// The field's view is an argument of its own: wave-uniform, scalar registers.
+template <int MATS, int INF, bool LIT>
+__global__ __launch_bounds__(kBlock, CRT_SHADE_WAVES) void k_shade_guided(Params P, PathSoA S, PathSoA N, HitSoA H, ShadowSoA Q,
+                                                                          Counters *C, int cur, float4 *staging, int first, GuideView G) {
+  static_assert(LIT || !INF, "lights at infinity are lights");
+  __shared__ uint32_t sobol_tab[kArenaDwords];
+  shade_segment<MATS, INF, LIT, kArenaDwords, false, false, false, true>(P, S, N, H, Q, C, cur, staging, sobol_tab, (first & 1) != 0,
+                                                                         (first & 2) != 0, nullptr, nullptr, nullptr, &G);
 }
 
 // ---- volume: the regions a segment crosses (volume.hip.h), between extend and shade of a volume render ----
@@ -2130,6 +2167,7 @@ static const InstanceRow<ShadowFn> kShadowRows[] = {CRT_INSTANCES_SHADOW(CRT_ROW
 static const InstanceRow<ShadeVolFn> kShadeVolRows[] = {CRT_INSTANCES_SHADE_VOL(CRT_ROW)};
 static const InstanceRow<ExtendFacesFn> kExtendFacesRows[] = {CRT_INSTANCES_EXTEND_FACES(CRT_ROW)};
 static const InstanceRow<ShadeFacesFn> kShadeFacesRows[] = {CRT_INSTANCES_SHADE_FACES(CRT_ROW)};
+static const InstanceRow<ShadeGuidedFn> kShadeGuidedRows[] = {CRT_INSTANCES_SHADE_GUIDED(CRT_ROW)};
 static const InstanceRow<CameraFn> kCameraRows[] = {CRT_INSTANCES_CAMERA(CRT_ROW)};
 static const InstanceRow<CameraVertexFn> kCameraVertexRows[] = {CRT_INSTANCES_CAMERA_VERTEX(CRT_ROW)};
 #undef CRT_ROW
@@ -2152,6 +2190,13 @@ int resolve_kernels(const LaunchPlan &plan, BatchKernels &k) {
     if (plan.volumes || plan.fused || plan.camera_trace || plan.shade_piped() || !plan.path.none()) return CRT_ERR_UNSUPPORTED;
     if (!find_instance(kExtendFacesRows, plan.extend, k.extend_faces) || !find_instance(kShadeFacesRows, plan.shade, k.shade_faces) ||
         !find_instance(kShadowRows, plan.shadow_key, k.shadow) || !k.extend_faces || !k.shade_faces)
+      return CRT_ERR_UNSUPPORTED;
+    return CRT_OK;
+  }
+  if (plan.guided) {  // guided renders: the GUIDED instance in the place of shade, per stage, nothing else new
+    if (plan.volumes || plan.fused || plan.camera_trace || plan.cam_compact || plan.shade_piped() || !plan.path.none()) return CRT_ERR_UNSUPPORTED;
+    if (!find_instance(kExtendRows, plan.extend, k.extend) || !find_instance(kShadeGuidedRows, plan.shade, k.shade_guided) ||
+        !find_instance(kShadowRows, plan.shadow_key, k.shadow) || !k.extend || !k.shade_guided)
       return CRT_ERR_UNSUPPORTED;
     return CRT_OK;
   }

@@ -145,7 +145,7 @@ inline bool engine_accepts(const EngineSelect &e, const DevScene &s, int kernel_
 // ---------------------------------------------------------------------------------------------
 enum KernelFamily : uint8_t { KF_NONE = 0, KF_EXTEND, KF_PATH, KF_SHADE, KF_SHADE_ENV, KF_SHADE_PIPE, KF_SHADOW, KF_SHADOW_CURVE, KF_SHADOW_CUBIC,
                                KF_SHADE_VOL, KF_VOLUME, KF_SHADOW_VOLUME, KF_EXTEND_DEFERRED, KF_CAMERA, KF_CAMERA_VERTEX,
-                               KF_EXTEND_FACES, KF_SHADE_FACES };
+                               KF_EXTEND_FACES, KF_SHADE_FACES, KF_SHADE_GUIDED };
 struct InstanceKey {  // a kernel template and its arguments, in the template's order (bools as 0 / 1)
   uint8_t family = KF_NONE;
   uint8_t arg[5] = {0, 0, 0, 0, 0};
@@ -230,6 +230,14 @@ struct InstanceKey {  // a kernel template and its arguments, in the template's 
   X(SHADE_FACES, k_shade_faces, 0, 0, false) X(SHADE_FACES, k_shade_faces, 0, 0, true) X(SHADE_FACES, k_shade_faces, 0, 1, true) X(SHADE_FACES, k_shade_faces, 0, 2, true) \
   X(SHADE_FACES, k_shade_faces, 1, 0, false) X(SHADE_FACES, k_shade_faces, 1, 0, true) X(SHADE_FACES, k_shade_faces, 1, 1, true) X(SHADE_FACES, k_shade_faces, 1, 2, true) \
   X(SHADE_FACES, k_shade_faces, 2, 0, false) X(SHADE_FACES, k_shade_faces, 2, 0, true) X(SHADE_FACES, k_shade_faces, 2, 1, true) X(SHADE_FACES, k_shade_faces, 2, 2, true)
+// Guided renders (PlanInputs::guided, crt_renderer_set_guiding). k_shade_guided<MATS, INF, LIT>: the shade instances whose
+// secondary vertices bounce through the guiding field and weigh NEE against the mixture pdf, instantiated like
+// k_shade_vol's — three waves, raw material records. A list of its own: a plan names them in `shade` with this family;
+// extend and shadow are the unbound plan's instances.
+#define CRT_INSTANCES_SHADE_GUIDED(X) /* k_shade_guided<MATS, INF, LIT> */ \
+  X(SHADE_GUIDED, k_shade_guided, 0, 0, false) X(SHADE_GUIDED, k_shade_guided, 0, 0, true) X(SHADE_GUIDED, k_shade_guided, 0, 1, true) X(SHADE_GUIDED, k_shade_guided, 0, 2, true) \
+  X(SHADE_GUIDED, k_shade_guided, 1, 0, false) X(SHADE_GUIDED, k_shade_guided, 1, 0, true) X(SHADE_GUIDED, k_shade_guided, 1, 1, true) X(SHADE_GUIDED, k_shade_guided, 1, 2, true) \
+  X(SHADE_GUIDED, k_shade_guided, 2, 0, false) X(SHADE_GUIDED, k_shade_guided, 2, 0, true) X(SHADE_GUIDED, k_shade_guided, 2, 1, true) X(SHADE_GUIDED, k_shade_guided, 2, 2, true)
 // The camera launches (LaunchPlan::camera_trace / camera_vertex): TABLE = the sample loop reads the per-pixel table,
 // ROOT_LDS = the cull reads the root from the LDS window, DRV = shade_early's table. Lists of their own: a plan names
 // the instance through camera_key().
@@ -281,6 +289,11 @@ struct PlanInputs {
   // material table; material_texture is indexed by geom_id whether or not the material table is deduplicated.
   // Not with volumes and not in the stats build: refused. false: exactly the plan of a renderer that never heard of it.
   bool faces = false;
+  // A guiding field is bound (crt_renderer_set_guiding): one launch per stage whatever the batch size, the GUIDED shade
+  // instances; extend and shadow as unbound. No fused kernel and no tail, no compact camera paths, no camera-trace /
+  // camera-vertex / pixel-table launch, no pipelined or slim shade, no derived material table. Lanes stay. Not in the
+  // stats build, not with volumes or textures: refused. false: exactly the plan of a renderer that never heard of it.
+  bool guided = false;
   // CRT_CAMERA_TRACE: 0 = generate and the first extend as before, 1 = k_camera wherever the result allows, 2 / 3 = the
   // same with every surviving ray deferred / with a one-entry stack (tests: the list and the deferred instance), -1 = the
   // host rule below
@@ -369,6 +382,8 @@ struct LaunchPlan {
   InstanceKey volume_key, shadow_volume_key;
   // Textured renders (PlanInputs::faces): `extend` names a KF_EXTEND_FACES instance, `shade` a KF_SHADE_FACES one.
   bool faces = false;
+  // Guided renders (PlanInputs::guided): `shade` names a KF_SHADE_GUIDED instance.
+  bool guided = false;
   // Camera rays traced where they are made (kernels/pathtrace.hip, k_camera): one launch generates, culls and traces the
   // batch's camera rays, one ray per lane, and writes their hit records; the first extend is the k_extend_deferred
   // instance over the few rays k_camera could not finish. `extend` names the same instance whatever this says.
@@ -434,17 +449,19 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
   pl.volumes = q.volumes;
   if (q.faces) pl.fused = false;  // textured renders likewise: the FACES instances are per-stage kernels
   pl.faces = q.faces;
+  if (q.guided) pl.fused = false;  // guided renders likewise: the GUIDED instances are per-stage kernels
+  pl.guided = q.guided;
   const bool stage = !pl.fused, lit = q.n_lights > 0;
   pl.wide = stage && e.wide;  // the fused kernel is a three-wave kernel whatever the scene prefers
   // The TAIL: from bounce `tail_from` on, what is left of the batch — roulette has ended all but a few paths per ten
   // thousand by then (bench: 6.6 M of 531 M rays at bounce 4, 0.1 M at bounce 6) — runs as ONE launch of the fused
   // path-loop kernel over the same segments instead of two or three launches per bounce up to the depth limit (bench,
   // depth 32: 52 launches, ~2 ms of a 137 ms step). Not for the stats build: its kernels count.
-  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights && !q.volumes && !q.faces;
+  const bool tail = stage && q.tail_from > 0 && !q.stats && !q.has_inf_lights && !q.volumes && !q.faces && !q.guided;
   if (tail) pl.tail_at = (uint32_t)q.tail_from;
   // camera paths as 16-byte records: per-stage launches of an UNLIT scene, pinhole camera, static scene
   // (not in a volume render: k_volume reads and rewrites the full form)
-  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion && !q.volumes && !q.faces) ? 1u : 0u;
+  pl.cam_compact = (q.cam_compact_build && stage && q.cam_compact_ok && !lit && !q.lens && !q.has_motion && !q.volumes && !q.faces && !q.guided) ? 1u : 0u;
   // The root cull (generate_segment_cull): per-stage launches of an image whose root is a node, when a camera ray that
   // escapes ends on the sky gradient — a depth limit above 0 and no light at infinity (their escaped rays take the
   // vertex step) — and where the frame shows enough background for it to pay (CRT_ROOT_CULL=1 skips that estimate). Not
@@ -495,6 +512,8 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
       pl.ext_cold = faces_cold;
       pl.extend = key(KF_EXTEND_FACES, width, faces_cold);
       pl.shade = key(KF_SHADE_FACES, q.mats_kind, q.has_env ? 2 : (q.has_inf_lights ? 1 : 0), lit);
+    } else if (q.guided) {  // the GUIDED instances: three-wave shade, raw records; extend and shadow as they are
+      pl.shade = key(KF_SHADE_GUIDED, q.mats_kind, q.has_env ? 2 : (q.has_inf_lights ? 1 : 0), lit);
     } else if (shade_wide && shade_pipe_fits(q) && q.noclassify_from > 0) pl.shade_early = key(KF_SHADE_PIPE, drv);
     pl.slim_state = pl.shade_piped() && q.no_emitter && q.slim_state != 0;
     if (pl.shadow) {
@@ -521,10 +540,11 @@ inline int plan_launches(const PlanInputs &q, LaunchPlan &out) {
   const bool ok = !(q.volumes && q.stats) &&  // the stats build counts no walk: refused (crt_render_samples_stats)
                   !(q.faces && (q.stats || q.volumes)) &&  // textured renders: no stats build, not beside volumes
                   !(q.faces && pl.extend.arg[0] == 2 && !q.wide_direct_build) &&
+                  !(q.guided && (q.stats || q.volumes || q.faces)) &&  // guided renders: no stats build, neither volumes nor textures
                   (pl.path.none() || engine_accepts(engine_of_width(e, q.scene, 0), q.scene, pl.path.arg[2])) &&
                   (pl.extend.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, pl.faces ? pl.extend.arg[1] : pl.extend.arg[2])) &&
                   (pl.shadow_key.none() || engine_accepts(engine_of_width(e, q.scene, width), q.scene, shadow_cold));
-  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.faces = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; pl.pixel_table = false; pl.cull_root_lds = false; }
+  if (!ok) { pl.path = pl.extend = pl.shade = pl.shade_early = pl.shadow_key = pl.volume_key = pl.shadow_volume_key = InstanceKey{}; pl.slim_state = false; pl.faces = false; pl.guided = false; pl.camera_trace = false; pl.camera_mode = 0; pl.camera_vertex = false; pl.pixel_table = false; pl.cull_root_lds = false; }
   out = pl;
   return ok ? CRT_OK : CRT_ERR_UNSUPPORTED;
 }

@@ -11,6 +11,8 @@
 
 #include "render_kernels.h"
 #include "face_textures_internal.h"
+#include "guiding_internal.h"
+#include "../../include/crt_render_guiding.h"
 
 namespace crt {
 
@@ -75,6 +77,11 @@ struct Renderer {
   // tables as the kernels take them. nullptr: none — every batch then runs what it ran before textures existed.
   CrtFaceTextures *faces = nullptr;
   dev::FaceView face_view{};
+  // The bound guiding field (crt_renderer_set_guiding): a reference of the renderer's own, and the view of its device image
+  // as the GUIDED shade instances take it — asked of guiding_device at the head of every render call, since
+  // crt_guiding_update may have rebuilt the image in between. nullptr: none — every batch runs what it ran before.
+  CrtGuiding *guiding = nullptr;
+  dev::GuideView guide_view{};
   uint32_t n_materials_given = 0;  // the caller's table at creation, before any deduplication: what material bindings index
   // What the root cull can save grows with the share of the frame that shows background; what it costs does not:
   // generate's slab tests and compaction, plane d beside the compact form. So the renderer looks first: the root step of
@@ -124,6 +131,7 @@ struct Renderer {
       if (B.done) (void)hipEventDestroy(B.done);
     }
     if (ev_start) (void)hipEventDestroy(ev_start);
+    guiding_release(guiding);  // behind the synchronised lanes, like the two below
     face_textures_release(faces);
     volumes_release(volumes);  // behind the synchronised lanes; the caller's stream is the caller's to drain (as for the scene)
     if (film) (void)hipFree(film);
@@ -232,6 +240,9 @@ struct Renderer {
     if (n_samples == 0) return CRT_OK;
     if (n_samples > 0xffffu) return CRT_ERR_BAD_ARG;
     (void)hipGetLastError();  // launches below are checked against a clean slate, not against an earlier call's error
+    // the field's current image: crt_guiding_update may have rebuilt it since the last call (the upload waits for the device)
+    if (guiding)
+      if (const int rc = guiding_device(guiding, guide_view)) return rc;
     last_stream = st;
     // how many lanes: one for the stats build and adaptive stopping (the active list changes between batches) and for
     // batches too small to fill the chip twice over
@@ -307,6 +318,7 @@ struct Renderer {
     in.class_stats = P.class_stats;
     in.volumes = volumes != nullptr;
     in.faces = faces != nullptr;
+    in.guided = guiding != nullptr;
   }
   // The per-pixel camera table (kernels/camera_pixel.hip.h), at creation: built where the plan of a large batch of this
   // renderer names it — asked of plan_launches itself, so the rule stays in one place. No memory for it (32 bytes per
@@ -348,6 +360,10 @@ struct Renderer {
       set_error_text("render refused: textured renders run neither the stats build nor beside volumes");
       return CRT_ERR_UNSUPPORTED;
     }
+    if (in.guided && (stats || in.volumes || in.faces)) {
+      set_error_text("render refused: guided renders run neither the stats build nor beside volumes or textures");
+      return CRT_ERR_UNSUPPORTED;
+    }
     if (plan_launches(in, last_plan) != CRT_OK) {
       set_error_text("render refused: the selected kernels (wide %d, cold %d / %d) cannot run this image (direct words %u, cold %u)",
                      (int)last_plan.wide, last_plan.ext_cold, last_plan.path_cold, P.scene.direct_leaves, P.scene.cold);
@@ -381,6 +397,7 @@ struct Renderer {
     const LaunchPlan plan = last_plan;
     if (plan.volumes != (volumes != nullptr)) return CRT_ERR_UNSUPPORTED;
     if (plan.faces != (faces != nullptr) || (plan.faces && !B.fplane)) return CRT_ERR_UNSUPPORTED;
+    if (plan.guided != (guiding != nullptr)) return CRT_ERR_UNSUPPORTED;
     BatchKernels k;
     if (const int rc = resolve_kernels(plan, k)) return rc;
     float4 *staging = B.staging;
@@ -441,6 +458,8 @@ struct Renderer {
         timed(0, st, [&] { hipLaunchKernelGGL(k.extend, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, d_tstats); });
       if (plan.faces) {  // the FACES shade instance (MatFace)
         timed(1, st, [&] { hipLaunchKernelGGL(k.shade_faces, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, first | ((int)it >= plan.noclassify_from ? 2 : 0), face_view, (const uint4 *)B.fplane); });
+      } else if (plan.guided) {  // the GUIDED shade instance (the field's view by value)
+        timed(1, st, [&] { hipLaunchKernelGGL(k.shade_guided, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, first | ((int)it >= plan.noclassify_from ? 2 : 0), guide_view); });
       } else if (plan.volumes) {  // the walk, then the VOL shade instance (plane c is k_volume's to write: never `first`), then the shadow segments' walk
         timed(3, st, [&] { hipLaunchKernelGGL(kStageKernels.volume, dim3(grid), dim3(kBlock), 0, st, p, S[cur], H, C, cur, first, vol); });
         timed(1, st, [&] { hipLaunchKernelGGL(k.shade_vol, dim3(grid), dim3(kBlock), 0, st, p, S[cur], S[1 - cur], H, Q, C, cur, staging, (int)it >= plan.noclassify_from ? 2 : 0, B.qseed); });
@@ -740,6 +759,10 @@ static int renderer_set_volumes(CrtRenderer *r, CrtVolumes *v) {
     set_error_text("crt_renderer_set_volumes: a per-face texture aggregate is bound; textures together with volumes are not built");
     return CRT_ERR_UNSUPPORTED;
   }
+  if (v && R.guiding) {
+    set_error_text("crt_renderer_set_volumes: a guiding field is bound; guided renders with volumes are not built");
+    return CRT_ERR_UNSUPPORTED;
+  }
   VolumesView view;
   if (v) {  // the image is uploaded here, not by the first batch
     const int rc = volumes_device(v, view);
@@ -776,6 +799,10 @@ static int renderer_set_face_textures(CrtRenderer *r, CrtFaceTextures *ft) {
     set_error_text("crt_renderer_set_face_textures: a volume aggregate is bound; textures together with volumes are not built");
     return CRT_ERR_UNSUPPORTED;
   }
+  if (ft && R.guiding) {
+    set_error_text("crt_renderer_set_face_textures: a guiding field is bound; guided renders with textures are not built");
+    return CRT_ERR_UNSUPPORTED;
+  }
   dev::FaceView view{};
   if (ft) {
     uint32_t n_geoms = 0, n_materials = 0;
@@ -806,9 +833,47 @@ int crt_renderer_set_face_textures(CrtRenderer *r, CrtFaceTextures *ft) {
   if (!r) return CRT_ERR_BAD_ARG;
   return abi_guard("crt_renderer_set_face_textures", [&] { return renderer_set_face_textures(r, ft); });  // nothing unwinds through the ABI
 }
+// The GUIDED instances read plane d of camera paths like every shade instance; a CRT_REGEN_FIRST build has shade work
+// camera paths out again in instances of its own, which hold no GUIDED form: that A/B build renders nothing guided.
+static int renderer_set_guiding(CrtRenderer *r, CrtGuiding *g) {
+  Renderer &R = r->r;
+  if (g == R.guiding) return CRT_OK;
+  if (g && kKernelBuild.regen_first) {
+    set_error_text("crt_renderer_set_guiding: a CRT_REGEN_FIRST build holds no guided shade instances");
+    return CRT_ERR_UNSUPPORTED;
+  }
+  if (g && R.volumes) {
+    set_error_text("crt_renderer_set_guiding: a volume aggregate is bound; guided renders with volumes are not built");
+    return CRT_ERR_UNSUPPORTED;
+  }
+  if (g && R.faces) {
+    set_error_text("crt_renderer_set_guiding: a per-face texture aggregate is bound; guided renders with textures are not built");
+    return CRT_ERR_UNSUPPORTED;
+  }
+  dev::GuideView view{};
+  if (g) {  // the image is uploaded here, not by the first batch
+    const int rc = guiding_device(g, view);
+    if (rc != CRT_OK) return rc;
+  }
+  // nothing of an earlier batch may be in flight when the old field's last reference goes (the buffers keep their shape:
+  // a guided batch has no plane of its own)
+  if (!CRT_HIP_OK(hipStreamSynchronize(R.last_stream))) return CRT_ERR_NO_DEVICE;
+  for (Renderer::Lane &B : R.lanes)
+    if (B.stream) (void)hipStreamSynchronize(B.stream);
+  guiding_retain(g);
+  guiding_release(R.guiding);
+  R.guiding = g;
+  R.guide_view = view;
+  return CRT_OK;
+}
+int crt_renderer_set_guiding(CrtRenderer *r, CrtGuiding *g) {
+  if (!r) return CRT_ERR_BAD_ARG;
+  return abi_guard("crt_renderer_set_guiding", [&] { return renderer_set_guiding(r, g); });  // nothing unwinds through the ABI
+}
 int crt_render_samples_stats(CrtRenderer *r, uint32_t sample_begin, uint32_t sample_count, void *stream,
                              CrtTravStats host_stats[2]) {
   if (!r || !host_stats) return CRT_ERR_BAD_ARG;
+  if (r->r.guiding) { set_error_text("crt_render_samples_stats: the stats build does not run guided renders"); return CRT_ERR_UNSUPPORTED; }
   if (r->r.faces) { set_error_text("crt_render_samples_stats: the stats build does not run textured renders"); return CRT_ERR_UNSUPPORTED; }
   if (r->r.volumes) { set_error_text("crt_render_samples_stats: the stats build does not run volume renders"); return CRT_ERR_UNSUPPORTED; }
   CrtTravStats *d = nullptr;
@@ -914,7 +979,7 @@ int crt_renderer_pipeline(const CrtRenderer *r, uint32_t out[3]) {
   out[0] = plan.fused ? 1u : 0u;
   out[1] = (plan.wide ? 1u : 0u) | (plan.shade_piped() ? 2u : 0u) | (plan.root_cull ? 4u : 0u) | (plan.slim_state ? 8u : 0u) |
            (plan.volumes ? 16u : 0u) | (plan.camera_trace ? 32u : 0u) | (plan.camera_vertex ? 64u : 0u) |
-           (plan.pixel_table ? 128u : 0u) | (plan.cull_root_lds ? 256u : 0u) | (plan.faces ? 512u : 0u);
+           (plan.pixel_table ? 128u : 0u) | (plan.cull_root_lds ? 256u : 0u) | (plan.faces ? 512u : 0u) | (plan.guided ? 1024u : 0u);
   out[2] = (uint32_t)r->r.grid;
   return CRT_OK;
 }

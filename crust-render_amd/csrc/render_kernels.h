@@ -9,6 +9,7 @@
 
 #include "crt_internal.h"
 #include "kernels/faces.hip.h"  // dev::FaceView, passed by value to the FACES shade instances
+#include "kernels/guiding.hip.h"  // dev::GuideView, passed by value to the GUIDED shade instances
 
 namespace crt {
 
@@ -160,6 +161,8 @@ using ShadeVolFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counter
 // kernel's arguments change — and the aggregate's tables (kernels/faces.hip.h).
 using ExtendFacesFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, CrtTravStats *, uint4 *);
 using ShadeFacesFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, dev::FaceView, const uint4 *);
+// Guided renders: the field's view (kernels/guiding.hip.h) — an argument of its own, as above.
+using ShadeGuidedFn = void (*)(Params, PathSoA, PathSoA, HitSoA, ShadowSoA, Counters *, int, float4 *, int, dev::GuideView);
 
 using GenerateFn = void (*)(Params, PathSoA, Counters *, uint32_t, uint32_t, float4 *);
 using VolumeFn = void (*)(Params, PathSoA, HitSoA, Counters *, int, int, VolArgs);
@@ -200,6 +203,7 @@ struct BatchKernels {
   ShadeVolFn shade_vol;
   ExtendFacesFn extend_faces;     // textured renders (LaunchPlan::faces): these two in the place of extend / shade
   ShadeFacesFn shade_faces;
+  ShadeGuidedFn shade_guided;     // guided renders (LaunchPlan::guided): in the place of shade
   ShadowFn shadow;
   CameraFn camera;                // the camera launch: one of the two, or neither (k_generate)
   CameraVertexFn camera_vertex;

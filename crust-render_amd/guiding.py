@@ -7,7 +7,8 @@ between passes (host arithmetic, single-threaded: the f32 sums depend on the ord
 whole bounce, shading.DeviceMaterials.scatter_guided — while tracing. Query and result records live
 in HBM as torch uint8 tensors; numpy structured dtypes give them field names on the host. There is no CPU fallback:
 sample, pdf and the guided bounce launch kernels of libcrt_amd.so. Building and updating the field, reading its image and
-its tallies need no device. The wavefront renderer does not use the field.
+its tallies need no device. The wavefront renderer reads a field only where one is bound to it
+(Renderer.set_guiding: the guided pass of render_guided; the renderer trains nothing — the field's owner does).
 """
 import ctypes as C
 

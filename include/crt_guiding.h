@@ -3,7 +3,8 @@
  * host-built image and three batched device functions over it, for a host integrator that keeps its own trace_path on
  * crt_intersect_n / crt_occluded_n and the shading seam and wants to turn on crust:pathGuiding (tracer.rs:245-403).
  * A header of its own beside crt.h: crt.h's set of declarations is pinned (tests/test_volumes.py, tests/test_abi.py).
- * Exported by the same library; include it after, or instead of, crt.h. The wavefront renderer does not use the field.
+ * Exported by the same library; include it after, or instead of, crt.h. The wavefront renderer reads a
+ * field only where one is bound to it (crt_render_guiding.h, crt_renderer_set_guiding: the guided pass; it trains nothing).
  *
  * The field lives on the host: crt_guiding_new / _update / _image / _stats touch no device. crt_guiding_update splats a
  * training pass in array order on one thread — the sums are f32 and the order is part of the result, as upstream's
